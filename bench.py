@@ -9,9 +9,12 @@ inputs (image, lens tables) resident in HBM.  One process per GPU; at N > 1 ever
 renders its own scene's stack (weak scaling) and, with --gather, the
 stacks are all-gathered over RCCL on a side stream overlapped with the next step.
 
-Prints ONE JSON line (rank 0).  `roofline` is the patch-PSF convolution kernel against
-the 8 TB/s HBM roofline with ALGORITHMIC bytes (24 B/pixel/slice, SURVEY.md §8d);
-`cpu_baseline` is the oracle (CPU restatement of the reference) timed on this host.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints
+the headline fields (metric, value, unit, ms_per_step, ...).  --full adds the untimed legs after
+the timed region: `roofline` is the patch-PSF convolution kernel against the 8 TB/s HBM
+roofline with ALGORITHMIC bytes (24 B/pixel/slice); `cpu_baseline` is the
+oracle (CPU restatement of the reference) timed on this host; `parity` compares the seed-0
+stack with it.  --dump-outputs DIR writes the last timed step's result as .npy files.
 """
 import argparse
 import json
@@ -120,11 +123,39 @@ def cpu_baseline(lens_path, img, dbar, fds, budget_s=30.0):
             "sample": f"{n} of {S} slices of the same 1024x1024 M1 stack (oracle: refocus+psf_map+render_psf_map), {dt:.1f} s"}, slices
 
 
+DUMP_MAX_ELEMENTS = 1 << 22            # per array: 16 MB of float32 (--dump-outputs writes at most 64 MB in all)
+DEFAULT_STEPS = {"m1": 200, "c3": 10, "m2": 20, "m1l": 50, "fit": 100}
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy, float32 (float64 stays float64).  An array of more than
+    DUMP_MAX_ELEMENTS elements is written as a fixed sample of its flattened elements: DUMP_MAX_ELEMENTS positions drawn
+    with numpy's PCG64 from seed 0 (with replacement, sorted), the same positions in every run of the same shape.  Gathered
+    on the tensor's device; call it outside the timed region."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype != torch.float64:
+            t = t.float()
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.Generator(np.random.PCG64(0)).integers(0, t.numel(), DUMP_MAX_ELEMENTS))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default: " + ", ".join(f"{k} {v}" for k, v in DEFAULT_STEPS.items()) + ")")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's timed steps, also run every untimed leg: soak, latency, one-stream and solo kernel "
+                         "timings, roofline, drop-in API, CPU baseline and parity (with the strict / edge modes) in m1; the 8-rank share "
+                         "in c3; the convolution-alone timing, composition and CPU baseline in m1l.  Off: set up, warm up, time, print")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32; "
+                         "arrays above 4 Mi elements as a fixed seeded sample, see dump_outputs)")
     ap.add_argument("--gather", action="store_true", help="all-gather the rendered stacks over RCCL (config 3)")
     ap.add_argument("--emulate-ranks", action="store_true",
                     help="run the --gpus N ranks on ONE GPU with the gloo backend (RCCL refuses two ranks per device): "
@@ -151,6 +182,8 @@ def main():
                          "m1l: M1-layered (SURVEY.md 8(d)): the depth MAP in 4 layers, one ray-traced PSF map per (slice, layer), per-pixel selection "
                          "fused into the stack convolution")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = DEFAULT_STEPS[args.mode]
     _thread_mark("after the imports")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -245,9 +278,10 @@ def main():
     for i in range(args.warmup):
         step(i)
     barrier()
+    last = None
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(i, True)
+        last = step(i, True)
     t_issued = time.perf_counter() - t0              # host side: every step of this rank queued
     if ring is not None:
         ring.drain()
@@ -267,6 +301,56 @@ def main():
         dist.all_gather(rows, own)
         ranks_seen = {"world_size": dist.get_world_size(), "backend": dist.get_backend(),
                       "own_ms_per_step": [round(float(r[0]), 4) for r in rows], "host_ms_per_step": [round(float(r[1]), 4) for r in rows]}
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, {"stack": last})        # [1,3,S,H,W] of the last timed step (seed steps - 1), rank 0
+
+    def kernel_flags():
+        """kernel error flags of every step so far (NaN residual / no valid chief ray -> the number is void): exit code 3"""
+        torch.cuda.synchronize(dev)
+        bits = 0
+        for p_ in pipe.plans:
+            bits |= int(p_.flags.item())
+            p_.flags.zero_()
+        if bits & 3:
+            print(f"bench: kernel flags 0x{bits:x} raised during the timed loop (bit0 NaN in Newton residual, bit1 no valid chief ray)",
+                  file=sys.stderr, flush=True)
+            raise SystemExit(3)
+        return bits
+
+    def headline(bits):
+        """the result line's fields that the timed steps themselves give"""
+        return {
+            "metric": "focal-stack MP/s (1024^2 x 10 slices, 11x11 PSF grid)",
+            "value": round(world * S * H * W / 1e6 * args.steps / dt, 2), "unit": "MP/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "streams": n_streams,
+            # who took part (the driver's first 8-rank run will want this): group size and backend as torch.distributed reports them,
+            # every rank's own ms per step and host-side queueing time before the max over ranks
+            "ranks_seen": ranks_seen,
+            # load and CPU quota of the host: on a shared, busy host the host-bound legs of --full (strict / edge pipelines at depth 4)
+            # read up to 2-4 x slower - profiles/r06_zz_bench_busy_host.json
+            "host": {"loadavg_1_5_15": [round(v, 1) for v in os.getloadavg()], "usable_cpus": usable_cpus()},
+            "config": {"workload": "rf50mm, 1024x1024 synthetic RGB + depth plane, 10 focus distances, 11x11 PSF grid, "
+                                   "ks 11, spp 2048 (+2048 chief), mode M1 (refocus -> psf_map -> render_psf_map)",
+                       "stacks_per_step_per_gpu": 1, "pupil_samples": "device RNG" if args.device_rng else "host torch RNG, reference call order",
+                       "gather": bool(ring is not None), "ranks_emulated_on_one_gpu": adist.emulated(),
+                       "value_is": f"pipelined throughput: steps queued back to back, {n_streams} stack(s) in flight on {n_streams} HIP stream(s) "
+                                   "of the GPU; latency_ms_p50 = one stack, host call to device idle",
+                       "arithmetic": "fp32 ray trace / PSF grid; convolution operands carried as fp16 hi+lo pairs "
+                                     "(>= 21-bit significand) on MFMA with fp32 accumulation, <= 2e-6 abs from the reference's fp32 conv2d"},
+            "flags": bits,
+        }
+
+    if not args.full:
+        bits = kernel_flags()
+        if rank == 0:
+            print(json.dumps(headline(bits)), flush=True)
+        if multi:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- untimed SOAK leg: the same pipelined step for >= 1 s, so that a sampler with a coarse cadence (the driver's gpu_busy reading,
     # rocm-smi) sees the GPU under this load at all - the timed region of the default command is ~7 ms
@@ -283,15 +367,7 @@ def main():
     soak_ms = (time.perf_counter() - t_soak) / max(n_soak, 1) * 1e3
 
     # ---- untimed: kernel error flags of every step so far (NaN residual / no valid chief ray -> the number is void)
-    torch.cuda.synchronize(dev)
-    bits = 0
-    for p_ in pipe.plans:
-        bits |= int(p_.flags.item())
-        p_.flags.zero_()
-    if bits & 3:
-        print(f"bench: kernel flags 0x{bits:x} raised during the timed loop (bit0 NaN in Newton residual, bit1 no valid chief ray)",
-              file=sys.stderr, flush=True)
-        raise SystemExit(3)
+    bits = kernel_flags()
 
     # ---- untimed: per-stack latency as SURVEY.md 8(d) defines it (first host call -> device idle), median of 20
     lat, lat_render = [], []
@@ -416,38 +492,16 @@ def main():
     if rank == 0:
         n_surf = len(lens.surfaces)
         steps_per_stack = 3 * (SPP + 2048) * GRID * GRID * n_surf * S         # rays x surfaces
-        res = {
-            "metric": "focal-stack MP/s (1024^2 x 10 slices, 11x11 PSF grid)",
-            "value": round(world * S * H * W / 1e6 * args.steps / dt, 2), "unit": "MP/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        res = headline(bits)
+        res.update({
             "latency_ms_p50": round(float(np.median(lat)) * 1e3, 4),
             # SURVEY.md 8(d)'s metric as defined there: S x H x W / (first host call -> device idle, one stack, median of 20)
             "value_survey_8d": round(S * H * W / 1e6 / float(np.median(lat)), 2),
             "latency_ms_p50_render_call_only": round(float(np.median(lat_render)) * 1e3, 4) if lat_render else None,
-            "streams": n_streams,
-            # who took part (the driver's first 8-rank run will want this): group size and backend as torch.distributed reports them,
-            # every rank's own ms per step and host-side queueing time before the max over ranks
-            "ranks_seen": ranks_seen,
-            # the GPU boxes are shared hosts (256 logical CPUs, a 16-CPU quota per job, load averages of 15-30 from other jobs): the
-            # host-bound legs (strict / edge pipelines at depth 4) read up to 2-4 x slower on a busy host - profiles/r06_zz_bench_busy_host.json
-            "host": {"loadavg_1_5_15": [round(v, 1) for v in os.getloadavg()], "usable_cpus": usable_cpus()},
             "soak": {"ms_per_step": round(soak_ms, 4), "steps": n_soak, "seconds": round(soak_ms * n_soak / 1e3, 2),
                      "what": "the same pipelined step queued for >= 1 s after the timed region (untimed leg; synchronised every 64 steps)"},
             "one_stream": {"ms_per_step": round(one_stream_ms, 4), "value": round(S * H * W / 1e6 / (one_stream_ms * 1e-3), 2), "steps": n_one,
                            "what": "the same step queued on ONE HIP stream (every kernel alone on the device; untimed leg of this rank)"},
-            "config": {"workload": "rf50mm, 1024x1024 synthetic RGB + depth plane, 10 focus distances, 11x11 PSF grid, "
-                                   "ks 11, spp 2048 (+2048 chief), mode M1 (refocus -> psf_map -> render_psf_map)",
-                       "stacks_per_step_per_gpu": 1, "pupil_samples": "device RNG" if args.device_rng else "host torch RNG, reference call order",
-                       "gather": bool(ring is not None), "ranks_emulated_on_one_gpu": adist.emulated(),
-                       "value_is": f"pipelined throughput: steps queued back to back, {n_streams} stack(s) in flight on {n_streams} HIP stream(s) "
-                                   "of the GPU; latency_ms_p50 = one stack, host call to device idle",
-                       "kernel_times_from": f"untimed solo leg after the timed region: the same stacks back to back on ONE stream, {len(solo)} "
-                                            "of them with events on the kernels' dispatches (kernels of different stacks overlap in the "
-                                            "timed region when streams > 1)",
-                       "arithmetic": "fp32 ray trace / PSF grid; convolution operands carried as fp16 hi+lo pairs "
-                                     "(>= 21-bit significand) on MFMA with fp32 accumulation, <= 2e-6 abs from the reference's fp32 conv2d"},
             "roofline": {"kernel": {"v": "conv_psf_map_kernel<11,5> (packed fp32 FMA)",
                                     "t": "conv_psf_map_mfma_kernel<11,5> (Toeplitz GEMM, fp16x3 operand split, fp32 accumulate)"}.get(
                                         os.environ.get("AADFF_CONV_PATH", "s")[0],
@@ -483,9 +537,10 @@ def main():
                       "us_per_stack": round(psf_ms * 1e3, 2), "ray_surface_steps_per_stack": steps_per_stack,
                       "ray_surface_steps_per_s": round(steps_per_stack / (psf_ms * 1e-3), 0),
                       "frac_of_step_one_stream": round(psf_ms / one_stream_ms, 4), "bound": "valu",
-                      "valu_busy": valu, "valu_busy_source": valu_source},
-            "flags": bits,
-        }
+                      "valu_busy": valu, "valu_busy_source": valu_source}})
+        res["config"]["kernel_times_from"] = (f"untimed solo leg after the timed region: the same stacks back to back on ONE stream, {len(solo)} "
+                                              "of them with events on the kernels' dispatches (kernels of different stacks overlap in the "
+                                              "timed region when streams > 1)")
         if world == 1:
             # the reference's OWN loops through the drop-in API (no StackPlan / StackPipeline): what a reference script gets
             try:
@@ -743,7 +798,7 @@ def main_c3(args):
     rend = SceneUnitRenderer(lens, scenes, S, GRID, KS, SPP, streams=c3_streams)
     n_units = n_scenes * S
     block = int(os.environ.get("AADFF_C3_BLOCK", "0")) or adist.scene_block(n_units, S, world)
-    steps, warm = (min(args.steps, 10) if args.steps == 200 else args.steps), min(args.warmup, 2)
+    steps, warm = args.steps, min(args.warmup, 2)
     multi = world > 1 or adist.grouped()               # AADFF_FORCE_GROUP=1: the gather branch on a one-rank RCCL group
     side = torch.cuda.Stream(dev) if multi else None
 
@@ -770,8 +825,10 @@ def main_c3(args):
         dist.barrier()
     dt = adist.all_reduce_max(time.perf_counter() - t0)
     rend.check_flags()
+    if args.dump_outputs and rank == 0 and steps:
+        dump_outputs(args.dump_outputs, {"gathered": full})     # [units,3,H,W] as every rank holds it after the last timed step
     share8 = None
-    if world == 1:
+    if world == 1 and args.full:
         # What ONE rank of an 8-rank job has to do, measured here (untimed leg): rank 0's share of the 8-way partition
         # rendered on this GPU without peers - its launches, and the host draws it replicates, go with the number of scenes
         # it touches, so this is NOT t1 / 8 by construction (tools/c3_share_probe.py sweeps partitions and rank counts).
@@ -801,7 +858,7 @@ def main_c3(args):
                        "the round-robin partition u = r mod 8 is listed beside it). With the gather a step cannot be shorter than "
                        "gather_floor_ms_at_8 (each rank receives 7/8 of the set) plus the last row's exposed part, so the gathered "
                        "configuration is link-bound and the >= 6x target of north_star is a no-gather target"}
-        if world == 1:
+        if share8 is not None:
             t1 = dt / steps * 1e3
             t8 = share8["block"]["ms"]
             rows8 = adist.padded_share(n_units, 8, share8["block"]["units_per_block"]) // share8["block"]["units_per_block"]
@@ -859,7 +916,7 @@ def main_m2(args):
     net.mlp_precision = os.environ.get("AADFF_M2_PRECISION", "fp32")       # "fp16": opt-in single-pass mode of the fused kernel
     img = torch.from_numpy(synth_rgb(H, W, seed=1234 + rank))[None].to(dev)
     depth_m = (torch.from_numpy(synth_depth_mm(H, W, seed=5678 + rank))[None, None] / 1e3).to(dev)
-    steps = min(args.steps, 20) if args.steps == 200 else args.steps        # a step is ~31 ms
+    steps = args.steps                                                      # a step is ~31 ms
     warm = min(args.warmup, 3)
     evs = []
 
@@ -875,15 +932,18 @@ def main_m2(args):
         dist.barrier()
     torch.cuda.synchronize(dev)
     psfnet_pack.EVENT_HOOK = hook
+    out = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        render_focal_stack_m2(net, img, depth_m, S)
+        out = render_focal_stack_m2(net, img, depth_m, S)
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
     psfnet_pack.EVENT_HOOK = None
+    if args.dump_outputs and rank == 0 and out is not None:
+        dump_outputs(args.dump_outputs, {"stack": out[0], "focus_dist": out[1]})      # [1,3,S,H,W] and [1,S] of the last timed step
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -933,7 +993,7 @@ def main_m1l(args):
     depth_h = -torch.from_numpy(synth_depth_mm(H, W, seed=5678 + rank))[None, None]
     img, depth = img_h.to(dev), depth_h.to(dev)
     fds = [float(f) for f in np.linspace(float(depth_h.max()), float(depth_h.min()), S)]       # nearest .. farthest (mm < 0)
-    steps = min(args.steps, 50) if args.steps == 200 else args.steps
+    steps = args.steps
     warm = min(args.warmup, 5)
     for i in range(warm):
         torch.manual_seed(i)
@@ -956,27 +1016,30 @@ def main_m1l(args):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # the convolution launch alone between two stream events (same image / maps / index as a step) and, for comparison, the whole
-    # composition it replaces
-    torch.manual_seed(7)
-    _, maps_d, lidx_d = render_focal_stack_m1_layered(lens, img, depth, fds, layers=L, grid=GRID, ks=KS, spp=SPP, return_parts=True)
-    out_d = torch.empty((1, 3, S, H, W), dtype=torch.float32, device=dev)
-    kms, comp = [], []
-    for i in range(20):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _abi.call("aadff_render_psf_map_stack_layered", _abi.ptr(img), _abi.ptr(maps_d), _abi.ptr(lidx_d), _abi.ptr(out_d), 1, 3, S, L, H, W, GRID, KS,
-                  _abi.stream_ptr(dev))
-        e1.record()
-        torch.cuda.synchronize(dev)
-        kms.append(e0.elapsed_time(e1))
-    for i in range(5):
-        t1 = time.perf_counter()
-        render_focal_stack_m1_layered(lens, img, depth, fds, layers=L, grid=GRID, ks=KS, spp=SPP, fused=False)
-        torch.cuda.synchronize(dev)
-        comp.append(time.perf_counter() - t1)
-    conv_ms = float(np.median(kms))
-    bytes_launch = (1 + S) * 3 * H * W * 4 + H * W                           # image once + S output slices + 1 B / pixel of layer index
+    if args.dump_outputs and rank == 0 and steps:
+        dump_outputs(args.dump_outputs, {"stack": out})          # [1,3,S,H,W] of the last timed step (seed 100 + steps - 1)
+    if args.full:
+        # the convolution launch alone between two stream events (same image / maps / index as a step) and, for comparison, the whole
+        # composition it replaces
+        torch.manual_seed(7)
+        _, maps_d, lidx_d = render_focal_stack_m1_layered(lens, img, depth, fds, layers=L, grid=GRID, ks=KS, spp=SPP, return_parts=True)
+        out_d = torch.empty((1, 3, S, H, W), dtype=torch.float32, device=dev)
+        kms, comp = [], []
+        for i in range(20):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            _abi.call("aadff_render_psf_map_stack_layered", _abi.ptr(img), _abi.ptr(maps_d), _abi.ptr(lidx_d), _abi.ptr(out_d), 1, 3, S, L, H, W, GRID, KS,
+                      _abi.stream_ptr(dev))
+            e1.record()
+            torch.cuda.synchronize(dev)
+            kms.append(e0.elapsed_time(e1))
+        for i in range(5):
+            t1 = time.perf_counter()
+            render_focal_stack_m1_layered(lens, img, depth, fds, layers=L, grid=GRID, ks=KS, spp=SPP, fused=False)
+            torch.cuda.synchronize(dev)
+            comp.append(time.perf_counter() - t1)
+        conv_ms = float(np.median(kms))
+        bytes_launch = (1 + S) * 3 * H * W * 4 + H * W                           # image once + S output slices + 1 B / pixel of layer index
     if rank == 0:
         res = {
             "metric": "focal-stack MP/s (M1-layered: RGB-D, depth map in 4 layers, 1024^2 x 10 slices, 11x11 PSF grid)",
@@ -985,17 +1048,19 @@ def main_m1l(args):
             "data": "synthetic",
             "config": {"workload": f"rf50mm, 1024x1024 synthetic RGB + depth MAP quantised into {L} layers, 10 focus distances, 11x11 PSF grid, ks 11, "
                                    f"spp 2048 (+2048 chief): {S * L} ray-traced PSF maps per stack, per-pixel selection fused into the stack convolution",
-                       "launches_per_stack": 3, "composition_ms_per_stack": round(float(np.median(comp)) * 1e3, 3),
-                       "composition": "the same three launches but S x L candidate slices through the stack convolution + torch.gather (L x the output bytes)"},
-            "roofline": {"kernel": "conv_psf_map_sbatch_kernel<24,4,false,false,LAYERED> (aadff_render_psf_map_stack_layered)", "bound": "hbm",
-                         "achieved": round(bytes_launch / (conv_ms * 1e-3) / 1e9, 2), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                         "frac": round(bytes_launch / (conv_ms * 1e-3) / HBM_PEAK, 4), "traffic": None,
-                         "basis": "(1 + S) x 12 B + 1 B of layer index per pixel (SURVEY.md 8(d) M1-layered; the index map is uint8 here)",
-                         "bytes_per_launch": bytes_launch, "kernel_ms": round(conv_ms, 4),
-                         "kernel_ms_note": "two stream events around the launch alone (same image, PSF maps and layer index as a step), median of 20",
-                         "tflops": round(2 * 3 * KS * KS * H * W * S * L / (conv_ms * 1e-3) / 1e12, 2)},
+                       "launches_per_stack": 3},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            res["config"].update({"composition_ms_per_stack": round(float(np.median(comp)) * 1e3, 3),
+                                  "composition": "the same three launches but S x L candidate slices through the stack convolution + torch.gather (L x the output bytes)"})
+            res["roofline"] = {"kernel": "conv_psf_map_sbatch_kernel<24,4,false,false,LAYERED> (aadff_render_psf_map_stack_layered)", "bound": "hbm",
+                               "achieved": round(bytes_launch / (conv_ms * 1e-3) / 1e9, 2), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                               "frac": round(bytes_launch / (conv_ms * 1e-3) / HBM_PEAK, 4), "traffic": None,
+                               "basis": "(1 + S) x 12 B + 1 B of layer index per pixel (SURVEY.md 8(d) M1-layered; the index map is uint8 here)",
+                               "bytes_per_launch": bytes_launch, "kernel_ms": round(conv_ms, 4),
+                               "kernel_ms_note": "two stream events around the launch alone (same image, PSF maps and layer index as a step), median of 20",
+                               "tflops": round(2 * 3 * KS * KS * H * W * S * L / (conv_ms * 1e-3) / 1e12, 2)}
+        if args.full and not args.no_cpu_baseline and world == 1:
             sys.path.insert(0, REPO)
             from oracle import psfnet as opsf
             from oracle.lens import OracleLens
@@ -1036,7 +1101,7 @@ def main_fit(args):
     net = PSFNet(os.path.join(REPO, "lenses", "rf50mm", "lens.json"), sensor_res=fit_res, kernel_size=KS, device=dev)
     net.psfnet.load_state_dict({k: torch.from_numpy(v) for k, v in mlp_state_dict(seed=4321).items()})
     from deeplens.psfnet import _TrainStep
-    steps = min(args.steps, 100) if args.steps == 200 else args.steps
+    steps = args.steps
     step = _TrainStep(net.psfnet, 1e-4, 10000, bs, KS * KS, dev, True, os.environ.get("AADFF_FIT_GRAPH", "1") != "0")
     t_data = [0.0]
 
@@ -1060,6 +1125,8 @@ def main_fit(args):
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
     plan.check_flags()
+    if args.dump_outputs and steps:                       # the network's parameters after the last timed training step
+        dump_outputs(args.dump_outputs, {f"param_{k.replace('.', '_')}": v for k, v in net.psfnet.state_dict().items()})
     print(json.dumps({
         "metric": f"PSFNet fit iterations/s (bs {bs} ray-traced PSF targets, spp {spp}, ks 11, bf16 MLP step)",
         "value": round(steps / dt, 2), "unit": "it/s", "n_gpus": 1, "steps": steps, "warmup": min(args.warmup, 10),

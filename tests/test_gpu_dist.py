@@ -105,12 +105,14 @@ def test_bench_c3_mode_one_rank_and_two_emulated_ranks():
     env["AADFF_C3_SCENES"] = "4"
     for gpus in (1, 2):
         extra = ["--gpus", "2", "--emulate-ranks"] if gpus == 2 else []
-        p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--mode", "c3", "--steps", "3", "--warmup", "1"] + extra,
+        p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--mode", "c3", "--steps", "3", "--warmup", "1"] + extra,
                            env=env, capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, p.stderr[-2000:]
         rec = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
         assert rec["n_gpus"] == gpus and rec["scaling"] == "strong" and rec["value"] > 0
         assert rec["config"]["gathered_shape"] == [40, 3, 1024, 1024] and "expected_scaling" in rec
+        if gpus == 1:                                   # the measured 8-rank share (one rank only, --full)
+            assert rec["expected_scaling"]["speedup_at_8_no_gather"] > 0 and rec["expected_scaling"]["speedup_at_8_with_gather"] > 0
 
 
 @pytest.mark.timeout(900)

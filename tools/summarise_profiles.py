@@ -1,17 +1,17 @@
 #!/usr/bin/env python3
-"""Copy the judged summaries of a tools/prof_r02.sh run from gpurun_out/<tag>_* into profiles/ (tracked):
+"""Copy the judged summaries of a tools/prof_r06.sh run from $PROF_OUT/<tag>_* (default prof_out/) into profiles/ (tracked):
 kernel-stats CSVs as they are, PMC counter CSVs reduced to one averaged row per kernel, plus two small JSON digests
 (profiles/psf_kernel_pmc.json, profiles/conv_traffic.json) that bench.py quotes as static context."""
 import collections, csv, glob, json, os, shutil, sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r02_a"
-G, P = os.path.join(REPO, "gpurun_out"), os.path.join(REPO, "profiles")
+G, P = os.environ.get("PROF_OUT") or os.path.join(REPO, "prof_out"), os.path.join(REPO, "profiles")
 
 
 def code_sha256(*sources):
     """sha256 of the kernel sources a digest belongs to: bench.py quotes a digest only while the tree still holds these sources.
-    Taken from gpurun_out/<tag>_code_sha256.json when the collection script wrote it AT COLLECTION TIME (tools/prof_r05.sh: the
+    Taken from $PROF_OUT/<tag>_code_sha256.json when the collection script wrote it AT COLLECTION TIME (tools/prof_r05.sh: the
     sources, common.h, include/aadff.h and the libaadff.so that ran - ADVICE r4: a digest summarised after an edit must not be
     stamped with the new hash); hashing the tree now is the fallback for older collections."""
     import hashlib
