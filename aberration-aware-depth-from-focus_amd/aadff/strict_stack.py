@@ -224,6 +224,9 @@ class StrictCounts:
         old = self.seen.get(key)
         self.seen[key] = bit if old is None or old.shape != bit.shape else (old | bit)
 
+    def bump(self, key, n=1):
+        self.stats[key] = self.stats.get(key, 0) + n
+
     def candidates(self, key, b, limit=4):
         """Count rows to try for batch b of a cheap level: the last truth, then single-surface deviations to every other count seen."""
         row = self.rows[key][b]
@@ -292,6 +295,17 @@ def _masks_to_counts(scratch, B):
     return counts_of_masks(scratch[:B * _abi.MAX_SURF].cpu().numpy().view(np.uint32).reshape(B, _abi.MAX_SURF))
 
 
+def _raise_if_nan(found):
+    """the reference's exit on a NaN residual of its non-differentiable Newton method (deeplens/surfaces.py:555-558)"""
+    if found:
+        raise FloatingPointError("found nan in ft in non-diff newton method.")
+
+
+def _same_bits(a, b):
+    """two lists of floats equal element by element, NaN matching NaN"""
+    return all((x == y) or (x != x and y != y) for x, y in zip(a, b))
+
+
 def _level1_batched(lens, uf, focus, S, tabs, n_tables, n_surf, bt, dev):
     """Round-4 form of level 1 (refocus, deeplens/optics.py:1155-1180): rays built on the host, one launch pair per surface, the
     focus-distance arithmetic on the host.  Returns (fd [S,2048] numpy, alive [S,2048] numpy bool, counts [S,MAX_SURF])."""
@@ -306,8 +320,7 @@ def _level1_batched(lens, uf, focus, S, tabs, n_tables, n_surf, bt, dev):
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
     scratch = _trace(od, dd, rad, GEO_SPP, S, tabs, n_tables, n_surf, bt, True, flag, dev)
     ro, rd, rra = od.cpu(), dd.cpu(), rad.cpu()
-    if int(flag.item()):
-        raise FloatingPointError("found nan in ft in non-diff newton method.")
+    _raise_if_nan(int(flag.item()))
     # (element-wise IEEE arithmetic: the same bits for all slices at once as slice by slice; the mean stays per slice)
     tt = (rd[..., 0] * ro[..., 0] + rd[..., 1] * ro[..., 1]) / (rd[..., 0] ** 2 + rd[..., 1] ** 2)
     tt = tt * rra
@@ -388,8 +401,7 @@ def _d_sensor_of(fd_all, alive, weights=None):
         if _MEAN_CHECKED[0] < _HostFast.CHECKS:
             _MEAN_CHECKED[0] += 1
             want = _d_sensor_loop(fd_all, alive)
-            same = all((a == b) or (a != a and b != b) for a, b in zip(out, want))
-            if not _HostFast.verify("mean", same):
+            if not _HostFast.verify("mean", _same_bits(out, want)):
                 out = want
     else:
         out = _d_sensor_loop(fd_all, alive)
@@ -423,8 +435,7 @@ def _level2_batched(lens, d_sensor, S, tabs, n_tables, n_surf, bt, dev):
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
     scratch = _trace(od, dd, rad, M, S, tabs, n_tables, n_surf, bt, bool(dfov[0, 0, 2] > 0), flag, dev)
     rd, rra = dd.cpu(), rad.cpu()
-    if int(flag.item()):
-        raise FloatingPointError("found nan in ft in non-diff newton method.")
+    _raise_if_nan(int(flag.item()))
     return rd[..., 0] / rd[..., 2], rra, _masks_to_counts(scratch, S)
 
 
@@ -529,8 +540,7 @@ def _level3_batched(lens, sel, points, pset, pc, pm, zs, bt_chief, bt_main, tabs
                   _abi.ptr(raw[b]), _abi.ptr(nrm), st)
     psf = raw / raw.sum(-1).sum(-1).unsqueeze(-1).unsqueeze(-1)                               # optics.py:978 (0/0 -> NaN like the reference)
     cnt = np.stack((_masks_to_counts(sc, B), _masks_to_counts(sm, B)), 1)
-    if flag.cpu().any():
-        raise FloatingPointError("found nan in ft in non-diff newton method.")
+    _raise_if_nan(flag.cpu().any())
     return psf, cnt, any_valid.cpu()
 
 
@@ -592,6 +602,7 @@ class _Stage:
         self.bt_green = torch.full((max(B, J),), t_green, dtype=i32, device=dev)
         self.zeros = torch.zeros(J, dtype=i32, device=dev)
         self.events = [torch.cuda.Event() for _ in sizes]
+        self.alt_out = {}                                    # (grid, ks) -> maps and centres of two-variant jobs' second variants
         # where the uniforms of every batch of pupil points sit in the stack's flat block of draws (stack_uniform_layout)
         from .focal_stack import stack_uniform_layout
         per, o_main, o_chief, per_l = stack_uniform_layout(spp, L)
@@ -705,6 +716,19 @@ def _nan_in_run(nan_bits, pred, curved):
     return bool(((np.asarray(nan_bits).astype(np.uint32) & ran) != 0)[..., curved].any())
 
 
+def _host_pupils(vec, u, off, ur, radius, z, out, per_slice=False):
+    """pupil points of the uniforms `ur` [..., 2, n] (theta, r) into the host block `out`: with `_sleef`'s vector routines in the
+    library (`_pupil_rows`: the uniforms of row i sit at u[off[i]:] and u[off[i] + n:] of the flat draw) or, where those are not
+    there, with torch (`_pupil_points`; `per_slice`: one call per leading index, see `_psf_pupils`)"""
+    n = ur.shape[-1]
+    if vec is not None:
+        _pupil_rows(vec, u, off, off + n, n, radius, z, out)
+        return
+    out = out.view(ur.shape[:-2] + (n, 3))
+    for k in (range(len(ur)) if per_slice else (slice(None),)):
+        out[k].copy_(_pupil_points(ur[k][..., 0, :], ur[k][..., 1, :], radius, z))
+
+
 def _speculate_small(counts, key, st, lvl, S, n, curved, order, launch, stream, after_first_submit=None):
     """A cheap level (S batches of n rays) on speculated counts: every batch is traced under each candidate row of the table at
     once (`StrictCounts.candidates`: 2048-ray batches cost nothing, a second round trip costs 60-100 us), the first candidate whose
@@ -729,11 +753,10 @@ def _speculate_small(counts, key, st, lvl, S, n, curved, order, launch, stream, 
             after_first_submit = None
         yield ev
         r = st.result(lvl)
-        counts.stats["fused"] += 1
+        counts.bump("fused")
         bits = r[2 * J * n:2 * J * n + J * 2 * MS].view(np.uint32).reshape(J, 2, MS)
         ok, fix = check_counts(bits[:, 0], pred, curved, order)
-        if _nan_in_run(bits[ok, 1], pred[ok], curved):
-            raise FloatingPointError("found nan in ft in non-diff newton method.")
+        _raise_if_nan(_nan_in_run(bits[ok, 1], pred[ok], curved))
         nxt = {}
         for j, (b, row) in enumerate(cand):
             if done[b]:
@@ -749,7 +772,7 @@ def _speculate_small(counts, key, st, lvl, S, n, curved, order, launch, stream, 
             counts.learn(key, truth)
             return out0, out1
         cand = [(b, row) for b, row in nxt.items() if not done[b]]
-        counts.stats["fused_replays"] += 1
+        counts.bump("fused_replays")
     return None
 
 
@@ -757,12 +780,128 @@ def _speculate_small(counts, key, st, lvl, S, n, curved, order, launch, stream, 
 def strict_psf_maps(lens, depth_plane_mm, focus, grid, ks, spp, fused=None):
     """PSF maps [S,3,g*ks,g*ks] (device) of a strict-parity lens for the focus distances `focus`, all field points on the plane
     `depth_plane_mm`; leaves the lens focused at the last distance, like the reference's loop."""
-    steps = _strict_psf_maps_steps(lens, depth_plane_mm, focus, grid, ks, spp, fused)
-    try:
-        while True:
-            next(steps).synchronize()                        # every yield is the event of a launch whose result the next step reads
-    except StopIteration as done:
-        return done.value
+    return _run_steps(_strict_psf_maps_steps(lens, depth_plane_mm, focus, grid, ks, spp, fused))
+
+
+class _StackCall:
+    """What one call of `_strict_psf_maps_steps` sets up in front of level 1, read by the levels below: shapes, tables, the count
+    table, the draws (in the reference's order: one flat draw = the same generator stream as call by call), the staging blocks and
+    streams of the fused form.  `native`: the native host driver has carried the call so far (levels 1 and 2 clear it when they
+    fall back to the Python form); `edge`: the `_EdgeStage` of an edge stack, else None."""
+    __slots__ = ("lens", "dev", "phase", "focus", "grid", "ks", "spp", "S", "L", "N", "B", "n_surf", "wv", "t_green", "tabs", "tab_dev",
+                 "counts", "curved", "keys", "fused", "per", "per_l", "st", "u", "uf", "um", "uc", "marks", "stream", "sp",
+                 "enp_z", "enp_rr", "pts", "depth", "fwd_order", "bwd_order", "hp", "vec", "s12", "sp12", "bt_green", "edge",
+                 "pupils_ready", "native", "nl", "pobj")
+
+    def __init__(self, lens, dev, depth_plane_mm, focus, grid, ks, spp, fused, phase):
+        from .focal_stack import stack_uniform_layout
+        if fused is None:
+            fused = os.environ.get("AADFF_STRICT_FUSED", "1") != "0"
+        self.lens, self.dev, self.phase, self.focus, self.grid, self.ks, self.spp = lens, dev, phase, focus, grid, ks, spp
+        S, L, N = self.S, self.L, self.N = len(focus), len(WAVE_RGB), grid * grid
+        B = self.B = S * L
+        self.n_surf = len(lens.surfaces)
+        wv = self.wv = list(WAVE_RGB) + ([] if DEFAULT_WAVE in WAVE_RGB else [DEFAULT_WAVE])
+        t_green = self.t_green = wv.index(DEFAULT_WAVE)
+        self.tabs, self.tab_dev = _tables(lens, wv), lens._table(wv)
+        counts = self.counts = StrictCounts.of(lens)
+        self.curved = _curved(lens)
+        keys = self.keys = (("focus", S), ("fov", S), ("psf", B, N, spp))
+        need = keys if phase == "all" else (keys[:2] if phase == "focus" else keys[2:])
+        fused = self.fused = fused and all(k in counts.rows for k in need)      # no table yet: this call is the seed run (round-4 form throughout)
+        st = self.st = _Stage.of(lens, dev, S, L, N, spp, t_green, phase) if fused else None
+
+        # ---- the draws, in the reference's order (one flat draw = the same generator stream as call by call)
+        per, _, _, per_l = stack_uniform_layout(spp, L)
+        if phase == "focus":
+            per = 2 * GEO_SPP
+        elif phase == "psf":
+            per = L * per_l
+        self.per, self.per_l = per, per_l
+        eb = None
+        if fused and is_edge(lens) and phase != "focus":
+            # the fast kernel of level 3 samples the pupil itself from the raw uniforms: they are drawn straight into the pinned block
+            # its upload starts from (the previous stack's upload out of that block has long completed - its event is checked all the same)
+            eb = st.edge_buffers(dev, S, L, N, per, ks)
+            if eb["busy"]:
+                eb["uploaded"].synchronize()
+            u = lens.sampler.rand_into(eb["h_u"]).view(S, per)
+        else:
+            u = lens.sampler.rand_block([S * per]).cpu().reshape(S, per)
+        self.u, self.uf, self.um, self.uc = u, None, None, None
+        if phase != "psf":
+            self.uf = u[:, :2 * GEO_SPP].reshape(S, 2, GEO_SPP)
+        if phase != "focus":
+            rest = u[:, (2 * GEO_SPP if phase == "all" else 0):].reshape(S, L, per_l)
+            self.um = rest[:, :, :2 * spp].reshape(S, L, 2, spp)
+            self.uc = rest[:, :, 2 * spp:].reshape(S, L, 2, GEO_SPP)
+
+        self.marks = [("start", time.perf_counter())] if os.environ.get("AADFF_STRICT_TIMING") == "1" else None
+        self.stream = torch.cuda.current_stream(dev)
+        self.sp = _abi.stream_ptr(dev)
+        self.enp_z, self.enp_rr = lens.entrance_pupil()
+        self.pts = lens.point_source_grid(depth=depth_plane_mm, grid=grid, quater=False).reshape(-1, 3).float()
+        self.depth = float(depth_plane_mm)
+        self.fwd_order, self.bwd_order = list(range(self.n_surf)), list(range(self.n_surf - 1, -1, -1))
+        self.hp = self.vec = self.s12 = self.sp12 = None
+        if fused:
+            self.hp = st.h_pupil
+            self.vec = _sleef()
+            # the two short levels may run on a stream of their own (StrictPipeline: a high-priority one, so that they do not queue
+            # behind the psf_map launch of the stack in front); every level ends with a host wait, which orders them with level 3
+            s12 = getattr(lens, "_strict_fast_stream", None)
+            if s12 is None and eb is not None and phase == "all":
+                # an edge stack starts its PSF kernel BEFORE the short levels (provisional pass): they need a stream of their own
+                # also outside a pipeline, a high-priority one (their few workgroups take the first slots the PSF kernel frees)
+                s12 = lens._table_cache.get("edge-side-stream")
+                if s12 is None:
+                    s12 = lens._table_cache["edge-side-stream"] = torch.cuda.Stream(dev, priority=-1)
+            self.s12 = self.stream if s12 is None else s12
+            self.sp12 = C.c_void_p(self.s12.cuda_stream)
+        self.bt_green = st.bt_green if fused else torch.full((B,), t_green, dtype=torch.int32, device=dev)
+        self.edge = _EdgeStage(self, eb) if eb is not None else None
+        self.pupils_ready = _WORKER.submit(_psf_pupils, self) if fused and phase != "focus" else None
+        # levels 1 and 2 through the native host driver (csrc/stack_host.cpp): what the Python form does between two waits, as one
+        # call each; any status != 0 (a batch no candidate row confirms, a NaN residual) falls through to the Python form of that level
+        self.native = fused and phase == "all" and self.vec is not None and _HostNative.on
+        self.nl = self.pobj = None
+
+    def mark(self, name):
+        if self.marks is not None:
+            self.marks.append((name, time.perf_counter()))
+
+    def object_points(self, hfov):
+        """psf_diff's object points [S,N,3] of this call (computed once)"""
+        if self.pobj is None:
+            self.pobj = _object_points(self.lens, self.pts, hfov)
+        return self.pobj
+
+
+def _psf_pupils(c):
+    """the psf_map pupil points are not needed before level 3: a worker thread evaluates them (torch releases the GIL in sqrt / cos /
+    sin) while the calling thread goes through levels 1 and 2, which are launch and round-trip latency.  Slice by slice: below
+    ATen's grain size (32768 elements) an element-wise op stays on the calling thread - a second OpenMP team next to the main
+    thread's oversubscribes a CPU quota (spinning workers: 60-80 ms stalls were measured).  (edge: the chief rays stay with the fast
+    kernel, only the main points are needed in the reference's arithmetic.)  With `_sleef`'s routines: two calls into the library,
+    no interpreter lock held."""
+    st, hp = c.st, c.hp
+    _host_pupils(c.vec, c.u, st.off_main, c.um, c.enp_rr, c.enp_z, hp[st.n_pf:st.n_pf + st.n_pm], per_slice=True)
+    if c.edge is None:
+        _host_pupils(c.vec, c.u, st.off_chief, c.uc, c.enp_rr * 0.5, c.enp_z, hp[st.n_pf + st.n_pm:], per_slice=True)
+
+
+def _set_lens_state(lens, d_sensor, hfov, foclen, fnum):
+    """the lens is left focused at the last distance, like the reference's loop"""
+    lens._state_sync()
+    hs = lens._state_host
+    hs.d_sensor, hs.hfov, hs.tan_hfov = float(d_sensor[-1]), float(hfov[-1]), float(np.tan(hfov[-1]))
+    hs.foclen, hs.fnum = float(foclen[-1]), float(fnum[-1])
+    if lens._state_dev is not None:
+        lens._state_upload()
+
+
+# the timing segments of the short levels, recorded empty by a psf_map call (it has none): every call reports the same segment names
+_SHORT_LEVEL_MARKS = ("level 1 back on the host", "d_sensor", "level 2 rays", "level 2 back on the host", "hfov")
 
 
 def _strict_psf_maps_steps(lens, depth_plane_mm, focus, grid, ks, spp, fused=None, phase="all"):
@@ -772,550 +911,486 @@ def _strict_psf_maps_steps(lens, depth_plane_mm, focus, grid, ks, spp, fused=Non
     `phase`: "all" = a stack (refocus -> calc_fov -> psf_map per slice); "focus" = the refocus / calc_fov half only (the lens state is
     set, None returned) and "psf" = the psf_map half only at the lens's current state - what `Lensgroup.refocus` and `.psf_map` of a
     strict lens call (one state each): the same kernels, tables and checks, the draws of each call in the reference's order."""
-    from .focal_stack import stack_uniform_layout
     if ks > _abi.MAX_KS:
         raise ValueError(f"ks={ks} exceeds the kernels' limit {_abi.MAX_KS}")
-    if fused is None:
-        fused = os.environ.get("AADFF_STRICT_FUSED", "1") != "0"
-    t_enter = time.perf_counter()
-    S, L, N = len(focus), len(WAVE_RGB), grid * grid
-    B, MS = S * L, _abi.MAX_SURF
-    dev = lens._gpu()
-    n_surf = len(lens.surfaces)
-    wv = list(WAVE_RGB) + ([] if DEFAULT_WAVE in WAVE_RGB else [DEFAULT_WAVE])
-    t_green = wv.index(DEFAULT_WAVE)
-    tabs = _tables(lens, wv)
-    tab_dev = lens._table(wv)
-    counts = StrictCounts.of(lens)
-    curved = _curved(lens)
-    f32 = torch.float32
     assert phase in ("all", "focus", "psf")
-    keys = (("focus", S), ("fov", S), ("psf", B, N, spp))
-    need = keys if phase == "all" else (keys[:2] if phase == "focus" else keys[2:])
-    fused = fused and all(k in counts.rows for k in need)      # no table yet: this call is the seed run (round-4 form throughout)
-
-    # ---- the draws, in the reference's order (one flat draw = the same generator stream as call by call)
-    per, o_main, o_chief, per_l = stack_uniform_layout(spp, L)
-    if phase == "focus":
-        per = 2 * GEO_SPP
-    elif phase == "psf":
-        per = L * per_l
-    edge = is_edge(lens) and fused and phase != "focus"
-    eb = None
-    if edge:
-        # the fast kernel of level 3 samples the pupil itself from the raw uniforms: they are drawn straight into the pinned block
-        # its upload starts from (the previous stack's upload out of that block has long completed - its event is checked all the same)
-        eb = _Stage.of(lens, dev, S, L, N, spp, t_green, phase).edge_buffers(dev, S, L, N, per, ks)
-        if eb["busy"]:
-            eb["uploaded"].synchronize()
-        u = lens.sampler.rand_into(eb["h_u"]).view(S, per)
-    else:
-        u = lens.sampler.rand_block([S * per]).cpu().reshape(S, per)
-    uf = um = uc = None
-    if phase != "psf":
-        uf = u[:, :2 * GEO_SPP].reshape(S, 2, GEO_SPP)
-    if phase != "focus":
-        rest = u[:, (2 * GEO_SPP if phase == "all" else 0):].reshape(S, L, per_l)
-        um = rest[:, :, :2 * spp].reshape(S, L, 2, spp)
-        uc = rest[:, :, 2 * spp:].reshape(S, L, 2, GEO_SPP)
-
-    marks = [("start", time.perf_counter())] if os.environ.get("AADFF_STRICT_TIMING") == "1" else None
-    mark = (lambda name: marks.append((name, time.perf_counter()))) if marks is not None else (lambda name: None)
+    t_enter = time.perf_counter()
+    dev = lens._gpu()
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev)
-        sp = _abi.stream_ptr(dev)
-        enp_z, enp_rr = lens.entrance_pupil()
-        s0 = lens.surfaces[0]
-        pts = lens.point_source_grid(depth=depth_plane_mm, grid=grid, quater=False).reshape(-1, 3).float()
-        fwd_order, bwd_order = list(range(n_surf)), list(range(n_surf - 1, -1, -1))
-        st = None
-        bt_green = None
-        if fused:
-            st = _Stage.of(lens, dev, S, L, N, spp, t_green, phase)
-            hp = st.h_pupil
-            vec = _sleef()
-            # the two short levels may run on a stream of their own (StrictPipeline: a high-priority one, so that they do not queue
-            # behind the psf_map launch of the stack in front); every level ends with a host wait, which orders them with level 3
-            s12 = getattr(lens, "_strict_fast_stream", None)
-            if s12 is None and edge and phase == "all":
-                # an edge stack starts its PSF kernel BEFORE the short levels (provisional pass below): they need a stream of their
-                # own also outside a pipeline, a high-priority one (their few workgroups take the first slots the PSF kernel frees)
-                s12 = lens._table_cache.get("edge-side-stream")
-                if s12 is None:
-                    s12 = lens._table_cache["edge-side-stream"] = torch.cuda.Stream(dev, priority=-1)
-            s12 = stream if s12 is None else s12
-            sp12 = C.c_void_p(s12.cuda_stream)
-        prov = edge and phase == "all" and os.environ.get("AADFF_EDGE_PROVISIONAL", "1") != "0"
-        if edge:
-            maps = torch.empty((S, L, grid * ks, grid * ks), dtype=f32, device=dev)
-            centre = torch.empty((B, N, 2), dtype=f32, device=dev)
-            hin, nst, du, cnt = eb["h_in"], eb["nst"], eb["d_u"], eb["count"]
-            if eb.get("pts_key") != (float(depth_plane_mm), grid):
-                hin[nst:].view(f32).view(S, N, 3).copy_(pts.unsqueeze(0).expand(S, N, 3))
-                eb["pts_key"] = (float(depth_plane_mm), grid)
-                eb["d_in"][nst:].copy_(hin[nst:], non_blocking=True)
-            o_main_w = 0 if phase == "psf" else 2 * GEO_SPP
-            surf_bytes = C.sizeof(_abi.Surface)
-
-            def launch_edge(states_ptr, slope_ptr):
-                _abi.call("aadff_psf_points_edge", _ptr_at(eb["d_in"], nst), S, N, L, _abi.ptr(tab_dev), C.c_void_p(tab_dev.data_ptr() + t_green * n_surf * surf_bytes),
-                          lens._lens_const(), states_ptr, _ptr_at(du, o_main_w), spp, per, per_l, _ptr_at(du, o_main_w + 2 * spp), GEO_SPP, per, per_l, ks,
-                          EDGE_DELTA_MM, _abi.ptr(eb["raw"]), _abi.ptr(centre), slope_ptr, _ptr_at(cnt, 0), _abi.ptr(eb["list"]), EDGE_CAP, _ptr_at(cnt, B), sp)
-        def edge_struct():
-            """aadff_edge_stack_t of this stage's buffers (csrc/stack_host.cpp), built once per buffer set"""
-            es = eb.get("es")
-            if es is None:
-                es = eb["es"] = _abi.EdgeStack()
-                es.S, es.L, es.N, es.spp, es.ks, es.n_surf, es.n_tables, es.t_green, es.cap = S, L, N, spp, ks, n_surf, len(wv), t_green, EDGE_CAP
-                es.per, es.per_l, es.o_main, es.n_pm = per, per_l, o_main_w, st.n_pm
-                es.delta, es.pixel_size, es.lc = EDGE_DELTA_MM, float(lens.pixel_size), lens._lens_const()
-                es.tables_dev = tab_dev.data_ptr()
-                es.h_u, es.d_u, es.h_focus, es.d_focus = eb["h_u"].data_ptr(), du.data_ptr(), eb["h_focus"].data_ptr(), eb["d_focus"].data_ptr()
-                es.d_pts, es.states_prov = eb["d_in"].data_ptr() + 4 * nst, eb["states_prov"].data_ptr()
-                es.raw, es.slope, es.count, es.list, es.h_back = eb["raw"].data_ptr(), eb["slope"].data_ptr(), cnt.data_ptr(), eb["list"].data_ptr(), eb["h_back"].data_ptr()
-                es.h_par3, es.d_par3, es.pset, es.bt_main = st.h_par[2].data_ptr(), st.d_par[2].data_ptr(), st.pset.data_ptr(), st.bt_main.data_ptr()
-                es.h_pupil_main, es.d_pupil_main = hp.data_ptr() + 4 * st.n_pf, st.d_pupil.data_ptr() + 4 * st.n_pf
-                eb["es_keep"] = (tab_dev, hp)                    # what the struct points into beyond eb / st
-            return es
-
-        def provisional_pass():
-            if native:
-                rc = lib.aadff_edge_provisional(C.byref(edge_struct()), C.c_void_p(nl["focus"].ctypes.data), _abi.ptr(centre), sp)
-                if rc != 0:
-                    raise RuntimeError("aadff_edge_provisional failed: " + lib.aadff_last_error().decode(errors="replace"))
-                mark("provisional pass queued")
-                return
-            # ---- provisional pass (edge stacks): the PSF kernel needs lens states, and the exact ones come out of two host round trips
-            # (levels 1 and 2 below, ~1 ms of latency with the GPU idle).  The interior rays do not care about a few ulps of d_sensor /
-            # hfov - only the border decisions do, and those are taken by the re-trace in the exact world - so the fast refocus kernel
-            # provides PROVISIONAL states from the same draws and the fast PSF kernel starts right away, beside the short levels; the
-            # re-trace moves each centre into the exact world (csrc/strict_fused.hip: EdgeRetraceArgs).
-            du.copy_(eb["h_u"], non_blocking=True)
-            eb["h_focus"][:S] = torch.tensor([float(f) for f in focus], dtype=f32)
-            eb["d_focus"][:S].copy_(eb["h_focus"][:S], non_blocking=True)
-            cnt[B:].zero_()
-            _abi.call("aadff_refocus", _abi.ptr(eb["d_focus"]), S, _abi.ptr(du), GEO_SPP, per, C.c_void_p(tab_dev.data_ptr() + t_green * n_surf * surf_bytes),
-                      lens._lens_const(), _abi.ptr(eb["states_prov"]), sp)
-            launch_edge(_abi.ptr(eb["states_prov"]), _abi.ptr(eb["slope"]))
-            mark("provisional pass queued")
-        # (queued right behind level 1's launch, below: the host work of queueing it then overlaps the level-1 kernel)
-        if fused and phase != "focus":
-            def psf_pupils():
-                # the psf_map pupil points are not needed before level 3: a worker thread evaluates them (torch releases the GIL in
-                # sqrt / cos / sin) while this thread goes through levels 1 and 2, which are launch and round-trip latency.  Slice by
-                # slice: below ATen's grain size (32768 elements) an element-wise op stays on the calling thread - a second OpenMP
-                # team next to the main thread's oversubscribes a CPU quota (spinning workers: 60-80 ms stalls were measured)
-                # (edge: the chief rays stay with the fast kernel, only the main points are needed in the reference's arithmetic)
-                if vec is not None:                      # two calls into the library, no interpreter lock held
-                    _pupil_rows(vec, u, st.off_main, st.off_main + spp, spp, enp_rr, enp_z, hp[st.n_pf:st.n_pf + st.n_pm])
-                    if not edge:
-                        _pupil_rows(vec, u, st.off_chief, st.off_chief + GEO_SPP, GEO_SPP, enp_rr * 0.5, enp_z, hp[st.n_pf + st.n_pm:])
-                    return
-                pm_h = hp[st.n_pf:st.n_pf + st.n_pm].view(S, L, spp, 3)
-                pc_h = hp[st.n_pf + st.n_pm:].view(S, L, GEO_SPP, 3)
-                for k in range(S):
-                    pm_h[k].copy_(_pupil_points(um[k, :, 0], um[k, :, 1], enp_rr, enp_z))
-                    if not edge:
-                        pc_h[k].copy_(_pupil_points(uc[k, :, 0], uc[k, :, 1], enp_rr * 0.5, enp_z))
-
-            pupils_ready = _WORKER.submit(psf_pupils)
+        c = _StackCall(lens, dev, depth_plane_mm, focus, grid, ks, spp, fused, phase)
         if phase == "psf":                                   # psf_map at the lens's current state (the reference reads self.d_sensor / self.hfov)
-            hs0 = lens._state_sync()
-            d_sensor, hfov, foclen, fnum = [float(hs0.d_sensor)] * S, [float(hs0.hfov)] * S, [float(hs0.foclen)] * S, [float(hs0.fnum)] * S
-        got = None
-        # ---- levels 1 and 2 through the native host driver (csrc/stack_host.cpp): what the Python below does between two waits, as one
-        # call each; any status != 0 (a batch no candidate row confirms, a NaN residual) falls through to the Python form of that level
-        native = fused and phase == "all" and vec is not None and _HostNative.on
-        l1_done = l2_done = prov_done = False
-        if native:
-            nl = st.native_levels(lens, counts, keys, curved, tab_dev, len(wv), n_surf, S)
-            lv, lib = nl["lv"], _abi.load_library()
-            nl["focus"][:] = focus
-            if prov and os.environ.get("AADFF_EDGE_PROV_FIRST", "1") != "0":
-                # the provisional pass needs nothing but the draws: queued FIRST, the 0.36 ms of fast refocus + PSF kernel start while this
-                # thread is still in MKL for the focus rays' aperture points (level 1 then runs beside them on its high-priority stream)
-                provisional_pass()
-                prov_done = True
-            R2_first = float(torch.ones((), dtype=f32) * s0.r ** 2)
-            prev = vec[4](1) if vec[4] is not None else None                      # MKL: one thread for this thread's calls (see _pupil_rows)
-            try:
-                rc = lib.aadff_levels_focus_submit(C.byref(lv), C.c_void_p(u.data_ptr()), C.c_void_p(st.off_focus.ctypes.data), float(np.float32(np.pi)), R2_first,
-                                                   float(np.float32(s0.d.item())), C.c_void_p(nl["focus"].ctypes.data), vec[0], vec[1], vec[2], vec[3], sp12,
-                                                   C.c_void_p(nl["events"][0].cuda_event))
-            finally:
-                if prev is not None:
-                    vec[4](prev)
-            if rc != 0:
-                raise RuntimeError("aadff_levels_focus_submit failed: " + lib.aadff_last_error().decode(errors="replace"))
-            mark("level 1 rays")
-            if prov and not prov_done:
-                provisional_pass()
-                prov_done = True
-            yield nl["events"][0]
-            counts.stats["fused"] += 1
-            status = lib.aadff_levels_focus_finish(C.byref(lv), C.c_void_p(nl["chosen"].ctypes.data), C.c_void_p(nl["dsens"].ctypes.data), C.c_void_p(nl["scratch"].ctypes.data))
-            if status == 0:
-                d_sensor = [float(v) for v in nl["dsens"]]
-                if nl["checked"] < _HostFast.CHECKS:                               # the driver's mean against numpy's own, on its first uses
-                    nl["checked"] += 1
-                    J1, r1 = lv.J1, st.result(0)
-                    rows_v = np.stack([r1[j * GEO_SPP:(j + 1) * GEO_SPP].view(np.float32) for j in nl["chosen"]])
-                    rows_w = np.stack([r1[(J1 + j) * GEO_SPP:(J1 + j + 1) * GEO_SPP].view(np.float32) for j in nl["chosen"]])
-                    want = _d_sensor_loop(rows_v, rows_w > 0)
-                    if not all((a == b) or (a != a and b != b) for a, b in zip(d_sensor, want)):
-                        _HostNative.switch_off("np.mean of the focus distances")
-                        d_sensor = want
-                for z in d_sensor:
-                    assert z > 0, "sensor position is negative."
-                if not np.array_equal(nl["chosen"], nl["first"][0]):                # a batch took an alternative row: it becomes the prediction
-                    counts.learn(keys[0], np.stack([nl["cand"][0][j][1] for j in nl["chosen"]]))
-                l1_done = True
-                counts.stats["native"] = counts.stats.get("native", 0) + 1
-            else:
-                counts.stats["native_fallbacks"] = counts.stats.get("native_fallbacks", 0) + 1
-        if fused and phase != "psf" and not l1_done:
-            # every pupil point of the stack comes from the reference's host calls; the focus ones ride in front of level 1
-            if vec is not None:
-                _pupil_rows(vec, u, st.off_focus, st.off_focus + GEO_SPP, GEO_SPP, s0.r, s0.d.item(), hp[:st.n_pf])
-            else:
-                hp[:st.n_pf].view(S, GEO_SPP, 3).copy_(_pupil_points(uf[:, 0], uf[:, 1], s0.r, s0.d.item()))
-            with torch.cuda.stream(s12):
-                st.d_pupil[:st.n_pf].copy_(hp[:st.n_pf], non_blocking=True)
-            mark("level 1 rays")
-            # ---- level 1: refocus (deeplens/optics.py:1155-1180) - rays from the first surface's aperture points away from (0, 0, focus)
-            t = st.h_par[0][:S * 3].view(f32).view(S, 3)
-            t.zero_()
-            t[:, 2] = torch.tensor([float(f) for f in focus], dtype=f32)
-
-            def launch1(J, par, res):
-                G = st.G[0]
-                _abi.call("aadff_trace_rays_strict_fused", None, None, None, GEO_SPP, J, _abi.ptr(tab_dev), len(wv), n_surf, _abi.ptr(st.bt_green),
-                          _ptr_at(par, 0), _ptr_at(par, G), _abi.ptr(st.d_pupil), 1, 0, n_surf, 1, None, _ptr_at(par, G + st.J),
-                          _ptr_at(res, 2 * J * GEO_SPP), 1, 1, _ptr_at(res, 0), _ptr_at(res, J * GEO_SPP), _ptr_at(par, G), sp12)
-
-            got = yield from _speculate_small(counts, keys[0], st, 0, S, GEO_SPP, curved, fwd_order, launch1, s12,
-                                              after_first_submit=provisional_pass if prov and not prov_done else None)
-            if got is not None:
-                fd_all, alive, w_focus = got[0], got[1] > 0, got[1]
-        bt_green = st.bt_green if st is not None else torch.full((B,), t_green, dtype=torch.int32, device=dev)
-        if phase != "psf" and (not fused or got is None) and not l1_done:
-            if fused:
-                counts.stats["per_surface_replays"] += 1
-            fd_all, alive, cnt = _level1_batched(lens, uf, focus, S, tabs, len(wv), n_surf, bt_green[:S], dev)
-            w_focus = None
-            counts.learn(keys[0], cnt)
-        mark("level 1 back on the host")
-        if phase != "psf" and not l1_done:
-            d_sensor = _d_sensor_of(fd_all, alive, w_focus)
-        mark("d_sensor")
-        if native and l1_done:
-            # ---- level 2, native: sensor corners into the block, launch, wait, the confirmed jobs' tangents back
-            dsa = np.asarray(d_sensor, dtype=np.float32)
-            backward = not bool(nl["o2z"] - torch.tensor(d_sensor[0], dtype=f32) > 0)
-            rc = lib.aadff_levels_fov_submit(C.byref(lv), C.c_void_p(dsa.ctypes.data), float(np.float32(lens.r_last)), int(not backward), sp12,
-                                             C.c_void_p(nl["events"][1].cuda_event))
-            if rc != 0:
-                raise RuntimeError("aadff_levels_fov_submit failed: " + lib.aadff_last_error().decode(errors="replace"))
-            mark("level 2 rays")
-            yield nl["events"][1]
-            counts.stats["fused"] += 1
-            status = lib.aadff_levels_fov_finish(C.byref(lv), C.c_void_p(nl["chosen"].ctypes.data), C.c_void_p(nl["tan"].ctypes.data), C.c_void_p(nl["ra"].ctypes.data))
-            if status == 0:
-                tan_fov, rra = torch.from_numpy(nl["tan"]), torch.from_numpy(nl["ra"])
-                if not np.array_equal(nl["chosen"], nl["first"][1]):
-                    counts.learn(keys[1], np.stack([nl["cand"][1][j][1] for j in nl["chosen"]]))
-                l2_done = True
-            else:
-                counts.stats["native_fallbacks"] = counts.stats.get("native_fallbacks", 0) + 1
-        # ---- level 2: calc_fov (deeplens/optics.py:1187-1217) - S batches of 100 rays from the sensor corner, backward
-        if fused and phase != "psf" and not l2_done:
-            o1, o2 = _fov_geometry(lens, d_sensor)
-            M = o2.shape[0]
-            backward = not bool(o2[0, 2] - o1[0, 2] > 0)
-            st.h_par[1][:S * 3].view(f32).view(S, 3).copy_(o1)
-            st.h_par[1][S * 3:S * 3 + M * 3].view(f32).view(M, 3).copy_(o2)
-
-            def launch2(J, par, res):
-                G = st.G[1]
-                _abi.call("aadff_trace_rays_strict_fused", None, None, None, M, J, _abi.ptr(tab_dev), len(wv), n_surf, _abi.ptr(st.bt_green),
-                          _ptr_at(par, 0), _ptr_at(par, G), _ptr_at(par, S * 3), 1, 0, n_surf, int(not backward), None, _ptr_at(par, G + st.J),
-                          _ptr_at(res, 2 * J * M), 0, 2, _ptr_at(res, 0), _ptr_at(res, J * M), _abi.ptr(st.zeros), sp12)
-
-            mark("level 2 rays")
-            got = yield from _speculate_small(counts, keys[1], st, 1, S, M, curved, bwd_order if backward else fwd_order, launch2, s12)
-            if got is not None:
-                tan_fov, rra = torch.from_numpy(got[0]), torch.from_numpy(got[1])
-        elif not l2_done:
-            mark("level 2 rays")
-        if phase != "psf" and (not fused or got is None) and not l2_done:
-            if fused:
-                counts.stats["per_surface_replays"] += 1
-            tan_fov, rra, cnt = _level2_batched(lens, d_sensor, S, tabs, len(wv), n_surf, bt_green[:S], dev)
-            counts.learn(keys[1], cnt)
-        mark("level 2 back on the host")
-        if phase != "psf":
+            hs = lens._state_sync()
+            d_sensor, hfov, foclen, fnum = ([float(v)] * c.S for v in (hs.d_sensor, hs.hfov, hs.foclen, hs.fnum))
+            for name in _SHORT_LEVEL_MARKS:
+                c.mark(name)
+        else:
+            d_sensor = yield from _level1(c)
+            tan_fov, rra = yield from _level2(c, d_sensor)
             hfov, foclen, fnum = _fov_of(lens, tan_fov, rra)
-        mark("hfov")
-        if phase == "focus":                                 # refocus + calc_fov of the per-call API: the state is set, no PSFs
-            lens._state_sync()
-            hs = lens._state_host
-            hs.d_sensor, hs.hfov, hs.tan_hfov = float(d_sensor[-1]), float(hfov[-1]), float(np.tan(hfov[-1]))
-            hs.foclen, hs.fnum = float(foclen[-1]), float(fnum[-1])
-            if lens._state_dev is not None:
-                lens._state_upload()
-            return None
+            c.mark("hfov")
+            if phase == "focus":                             # refocus + calc_fov of the per-call API: the state is set, no PSFs
+                _set_lens_state(lens, d_sensor, hfov, foclen, fnum)
+                return None
         # ---- level 3: psf_map (deeplens/optics.py:888-1026) - per slice and wavelength spp x N main rays and 2048 x N chief rays
-        edge_native = bool(edge and native and prov and prov_done and l1_done and l2_done)
+        out = (yield from c.edge.level3(c, d_sensor, hfov, foclen, fnum)) if c.edge is not None else None
+        if out is None:
+            out = (yield from _level3_fused(c, d_sensor, hfov)) if c.fused else _level3_seed(c, d_sensor, hfov)
+        maps, any_valid = out
+        c.mark("level 3 done")
+        if c.marks is not None:
+            lens._strict_timing = [("draws and setup", round((c.marks[0][1] - t_enter) * 1e3, 3))] + \
+                                  [(b[0], round((b[1] - a[1]) * 1e3, 3)) for a, b in zip(c.marks, c.marks[1:])]
+    assert bool(any_valid.bool().all()), "No sampled rays is valid."
+    if phase == "psf":
+        return maps
+    _set_lens_state(lens, d_sensor, hfov, foclen, fnum)
+    lens._strict_stack_scalars = {"d_sensor": d_sensor, "hfov": hfov}
+    return maps
+
+
+# ---------------------------------------------------------------------------------------------------------------- levels 1 and 2
+def _level1(c):
+    """level 1: refocus (deeplens/optics.py:1155-1180) -> d_sensor [S] - through the native host driver, else on speculated counts
+    from Python, else (and in the seed run) in the per-surface form"""
+    st, S, counts, vec = c.st, c.S, c.counts, c.vec
+    s0 = c.lens.surfaces[0]
+    if c.native:
+        nl = c.nl = st.native_levels(c.lens, counts, c.keys, c.curved, c.tab_dev, len(c.wv), c.n_surf, S)
+        lv = nl["lv"]
+        nl["focus"][:] = c.focus
+        if c.edge is not None:
+            c.edge.provisional(c, first=True)
+        R2_first = float(torch.ones((), dtype=torch.float32) * s0.r ** 2)
+        prev = vec[4](1) if vec[4] is not None else None                      # MKL: one thread for this thread's calls (see _pupil_rows)
+        try:
+            _abi.call("aadff_levels_focus_submit", C.byref(lv), C.c_void_p(c.u.data_ptr()), C.c_void_p(st.off_focus.ctypes.data), float(np.float32(np.pi)),
+                      R2_first, float(np.float32(s0.d.item())), C.c_void_p(nl["focus"].ctypes.data), vec[0], vec[1], vec[2], vec[3], c.sp12,
+                      C.c_void_p(nl["events"][0].cuda_event))
+        finally:
+            if prev is not None:
+                vec[4](prev)
+        c.mark("level 1 rays")
+        if c.edge is not None:
+            c.edge.provisional(c)
+        yield nl["events"][0]
+        counts.bump("fused")
+        status = _abi.load_library().aadff_levels_focus_finish(C.byref(lv), C.c_void_p(nl["chosen"].ctypes.data), C.c_void_p(nl["dsens"].ctypes.data),
+                                                               C.c_void_p(nl["scratch"].ctypes.data))
+        if status == 0:
+            d_sensor = [float(v) for v in nl["dsens"]]
+            if nl["checked"] < _HostFast.CHECKS:                               # the driver's mean against numpy's own, on its first uses
+                nl["checked"] += 1
+                J1, r1 = lv.J1, st.result(0)
+                rows_v = np.stack([r1[j * GEO_SPP:(j + 1) * GEO_SPP].view(np.float32) for j in nl["chosen"]])
+                rows_w = np.stack([r1[(J1 + j) * GEO_SPP:(J1 + j + 1) * GEO_SPP].view(np.float32) for j in nl["chosen"]])
+                want = _d_sensor_loop(rows_v, rows_w > 0)
+                if not _same_bits(d_sensor, want):
+                    _HostNative.switch_off("np.mean of the focus distances")
+                    d_sensor = want
+            for z in d_sensor:
+                assert z > 0, "sensor position is negative."
+            if not np.array_equal(nl["chosen"], nl["first"][0]):                # a batch took an alternative row: it becomes the prediction
+                counts.learn(c.keys[0], np.stack([nl["cand"][0][j][1] for j in nl["chosen"]]))
+            counts.bump("native")
+            c.mark("level 1 back on the host")
+            c.mark("d_sensor")
+            return d_sensor
+        counts.bump("native_fallbacks")
+        c.native = False
+    got = None
+    if c.fused:
+        # every pupil point of the stack comes from the reference's host calls; the focus ones ride in front of level 1
+        _host_pupils(vec, c.u, st.off_focus, c.uf, s0.r, s0.d.item(), c.hp[:st.n_pf])
+        with torch.cuda.stream(c.s12):
+            st.d_pupil[:st.n_pf].copy_(c.hp[:st.n_pf], non_blocking=True)
+        c.mark("level 1 rays")
+        # rays from the first surface's aperture points away from (0, 0, focus)
+        t = st.h_par[0][:S * 3].view(torch.float32).view(S, 3)
+        t.zero_()
+        t[:, 2] = torch.tensor([float(f) for f in c.focus], dtype=torch.float32)
+
+        def launch1(J, par, res):
+            G = st.G[0]
+            _abi.call("aadff_trace_rays_strict_fused", None, None, None, GEO_SPP, J, _abi.ptr(c.tab_dev), len(c.wv), c.n_surf, _abi.ptr(st.bt_green),
+                      _ptr_at(par, 0), _ptr_at(par, G), _abi.ptr(st.d_pupil), 1, 0, c.n_surf, 1, None, _ptr_at(par, G + st.J),
+                      _ptr_at(res, 2 * J * GEO_SPP), 1, 1, _ptr_at(res, 0), _ptr_at(res, J * GEO_SPP), _ptr_at(par, G), c.sp12)
+
+        # (an edge stack's provisional pass is queued right behind the first launch: the host work of queueing it overlaps the kernel)
+        got = yield from _speculate_small(counts, c.keys[0], st, 0, S, GEO_SPP, c.curved, c.fwd_order, launch1, c.s12,
+                                          after_first_submit=None if c.edge is None else lambda: c.edge.provisional(c))
+    if got is None:
+        if c.fused:
+            counts.bump("per_surface_replays")
+        fd_all, alive, cnt = _level1_batched(c.lens, c.uf, c.focus, S, c.tabs, len(c.wv), c.n_surf, c.bt_green[:S], c.dev)
+        w_focus = None
+        counts.learn(c.keys[0], cnt)
+    else:
+        fd_all, alive, w_focus = got[0], got[1] > 0, got[1]
+    c.mark("level 1 back on the host")
+    d_sensor = _d_sensor_of(fd_all, alive, w_focus)
+    c.mark("d_sensor")
+    return d_sensor
+
+
+def _level2(c, d_sensor):
+    """level 2: calc_fov (deeplens/optics.py:1187-1217) - S batches of 100 rays from the sensor corner, backward -> (tan_fov, ra)
+    [S,100] host tensors; the same chain as level 1, the native driver only behind a native level 1"""
+    st, S, counts = c.st, c.S, c.counts
+    if c.native:
+        # sensor corners into the block, launch, wait, the confirmed jobs' tangents back
+        nl = c.nl
+        dsa = np.asarray(d_sensor, dtype=np.float32)
+        backward = not bool(nl["o2z"] - torch.tensor(d_sensor[0], dtype=torch.float32) > 0)
+        _abi.call("aadff_levels_fov_submit", C.byref(nl["lv"]), C.c_void_p(dsa.ctypes.data), float(np.float32(c.lens.r_last)), int(not backward),
+                  c.sp12, C.c_void_p(nl["events"][1].cuda_event))
+        c.mark("level 2 rays")
+        yield nl["events"][1]
+        counts.bump("fused")
+        status = _abi.load_library().aadff_levels_fov_finish(C.byref(nl["lv"]), C.c_void_p(nl["chosen"].ctypes.data), C.c_void_p(nl["tan"].ctypes.data),
+                                                             C.c_void_p(nl["ra"].ctypes.data))
+        if status == 0:
+            if not np.array_equal(nl["chosen"], nl["first"][1]):
+                counts.learn(c.keys[1], np.stack([nl["cand"][1][j][1] for j in nl["chosen"]]))
+            c.mark("level 2 back on the host")
+            return torch.from_numpy(nl["tan"]), torch.from_numpy(nl["ra"])
+        counts.bump("native_fallbacks")
+        c.native = False
+    got = None
+    if c.fused:
+        o1, o2 = _fov_geometry(c.lens, d_sensor)
+        M = o2.shape[0]
+        backward = not bool(o2[0, 2] - o1[0, 2] > 0)
+        st.h_par[1][:S * 3].view(torch.float32).view(S, 3).copy_(o1)
+        st.h_par[1][S * 3:S * 3 + M * 3].view(torch.float32).view(M, 3).copy_(o2)
+
+        def launch2(J, par, res):
+            G = st.G[1]
+            _abi.call("aadff_trace_rays_strict_fused", None, None, None, M, J, _abi.ptr(c.tab_dev), len(c.wv), c.n_surf, _abi.ptr(st.bt_green),
+                      _ptr_at(par, 0), _ptr_at(par, G), _ptr_at(par, S * 3), 1, 0, c.n_surf, int(not backward), None, _ptr_at(par, G + st.J),
+                      _ptr_at(res, 2 * J * M), 0, 2, _ptr_at(res, 0), _ptr_at(res, J * M), _abi.ptr(st.zeros), c.sp12)
+
+        c.mark("level 2 rays")
+        got = yield from _speculate_small(counts, c.keys[1], st, 1, S, M, c.curved, c.bwd_order if backward else c.fwd_order, launch2, c.s12)
+    else:
+        c.mark("level 2 rays")
+    if got is None:
+        if c.fused:
+            counts.bump("per_surface_replays")
+        tan_fov, rra, cnt = _level2_batched(c.lens, d_sensor, S, c.tabs, len(c.wv), c.n_surf, c.bt_green[:S], c.dev)
+        counts.learn(c.keys[1], cnt)
+    else:
+        tan_fov, rra = torch.from_numpy(got[0]), torch.from_numpy(got[1])
+    c.mark("level 2 back on the host")
+    return tan_fov, rra
+
+
+# ---------------------------------------------------------------------------------------------------------------- level 3
+class _EdgeStage:
+    """Level 3 of an edge stack over its stage's edge buffers: fast kernel (already running on provisional states, or launched here
+    on the exact ones) + strict re-trace of the rays at the window edge + normalisation, no host wait in between.  Built only for
+    edge stacks, in front of level 1, whose hooks queue the provisional pass (`provisional`).  It does not keep the call `c` (the
+    call keeps it: no reference cycle for the collector)."""
+    __slots__ = ("eb", "prov", "queued", "maps", "centre", "o_main", "green")
+
+    def __init__(self, c, eb):
+        S, L, N, B, f32 = c.S, c.L, c.N, c.B, torch.float32
+        self.eb, self.queued = eb, False
+        self.prov = c.phase == "all" and os.environ.get("AADFF_EDGE_PROVISIONAL", "1") != "0"
+        self.maps = torch.empty((S, L, c.grid * c.ks, c.grid * c.ks), dtype=f32, device=c.dev)
+        self.centre = torch.empty((B, N, 2), dtype=f32, device=c.dev)
+        hin, nst = eb["h_in"], eb["nst"]
+        if eb.get("pts_key") != (c.depth, c.grid):
+            hin[nst:].view(f32).view(S, N, 3).copy_(c.pts.unsqueeze(0).expand(S, N, 3))
+            eb["pts_key"] = (c.depth, c.grid)
+            eb["d_in"][nst:].copy_(hin[nst:], non_blocking=True)
+        self.o_main = 0 if c.phase == "psf" else 2 * GEO_SPP
+        self.green = C.c_void_p(c.tab_dev.data_ptr() + c.t_green * c.n_surf * C.sizeof(_abi.Surface))      # the green surface table
+
+    def _launch(self, c, states_ptr, slope_ptr):
+        eb, du, cnt = self.eb, self.eb["d_u"], self.eb["count"]
+        _abi.call("aadff_psf_points_edge", _ptr_at(eb["d_in"], eb["nst"]), c.S, c.N, c.L, _abi.ptr(c.tab_dev), self.green, c.lens._lens_const(), states_ptr,
+                  _ptr_at(du, self.o_main), c.spp, c.per, c.per_l, _ptr_at(du, self.o_main + 2 * c.spp), GEO_SPP, c.per, c.per_l, c.ks, EDGE_DELTA_MM,
+                  _abi.ptr(eb["raw"]), _abi.ptr(self.centre), slope_ptr, _ptr_at(cnt, 0), _abi.ptr(eb["list"]), EDGE_CAP, _ptr_at(cnt, c.B), c.sp)
+
+    def _struct(self, c):
+        """aadff_edge_stack_t of this stage's buffers (csrc/stack_host.cpp), built once per buffer set"""
+        eb, st = self.eb, c.st
+        es = eb.get("es")
+        if es is None:
+            es = eb["es"] = _abi.EdgeStack()
+            es.S, es.L, es.N, es.spp, es.ks, es.n_surf, es.n_tables, es.t_green, es.cap = c.S, c.L, c.N, c.spp, c.ks, c.n_surf, len(c.wv), c.t_green, EDGE_CAP
+            es.per, es.per_l, es.o_main, es.n_pm = c.per, c.per_l, self.o_main, st.n_pm
+            es.delta, es.pixel_size, es.lc = EDGE_DELTA_MM, float(c.lens.pixel_size), c.lens._lens_const()
+            es.tables_dev = c.tab_dev.data_ptr()
+            es.h_u, es.d_u, es.h_focus, es.d_focus = eb["h_u"].data_ptr(), eb["d_u"].data_ptr(), eb["h_focus"].data_ptr(), eb["d_focus"].data_ptr()
+            es.d_pts, es.states_prov = eb["d_in"].data_ptr() + 4 * eb["nst"], eb["states_prov"].data_ptr()
+            es.raw, es.slope, es.count, es.list, es.h_back = eb["raw"].data_ptr(), eb["slope"].data_ptr(), eb["count"].data_ptr(), eb["list"].data_ptr(), eb["h_back"].data_ptr()
+            es.h_par3, es.d_par3, es.pset, es.bt_main = st.h_par[2].data_ptr(), st.d_par[2].data_ptr(), st.pset.data_ptr(), st.bt_main.data_ptr()
+            es.h_pupil_main, es.d_pupil_main = c.hp.data_ptr() + 4 * st.n_pf, st.d_pupil.data_ptr() + 4 * st.n_pf
+            eb["es_keep"] = (c.tab_dev, c.hp)                # what the struct points into beyond eb / st
+        return es
+
+    def provisional(self, c, first=False):
+        """Level 1's hook: queues the provisional pass, once, if this stack has one - `first`: in front of the native driver's level-1
+        submit (the pass needs nothing but the draws: queued FIRST, the 0.36 ms of fast refocus + PSF kernel start while the host is
+        still in MKL for the focus rays' aperture points; AADFF_EDGE_PROV_FIRST=0 leaves it to the hook behind the submit).
+        The PSF kernel needs lens states, and the exact ones come out of two host round trips (levels 1 and 2, ~1 ms of latency
+        with the GPU idle).  The interior rays do not care about a few ulps of d_sensor / hfov - only the border decisions do, and
+        those are taken by the re-trace in the exact world - so the fast refocus kernel provides PROVISIONAL states from the same
+        draws and the fast PSF kernel starts right away, beside the short levels; the re-trace moves each centre into the exact
+        world (csrc/strict_fused.hip: EdgeRetraceArgs)."""
+        if not self.prov or self.queued or (first and os.environ.get("AADFF_EDGE_PROV_FIRST", "1") == "0"):
+            return
+        self.queued = True
+        eb = self.eb
+        if c.native:
+            _abi.call("aadff_edge_provisional", C.byref(self._struct(c)), C.c_void_p(c.nl["focus"].ctypes.data), _abi.ptr(self.centre), c.sp)
+        else:
+            eb["d_u"].copy_(eb["h_u"], non_blocking=True)
+            eb["h_focus"][:c.S] = torch.tensor([float(f) for f in c.focus], dtype=torch.float32)
+            eb["d_focus"][:c.S].copy_(eb["h_focus"][:c.S], non_blocking=True)
+            eb["count"][c.B:].zero_()
+            _abi.call("aadff_refocus", _abi.ptr(eb["d_focus"]), c.S, _abi.ptr(eb["d_u"]), GEO_SPP, c.per, self.green, c.lens._lens_const(),
+                      _abi.ptr(eb["states_prov"]), c.sp)
+            self._launch(c, _abi.ptr(eb["states_prov"]), _abi.ptr(eb["slope"]))
+        c.mark("provisional pass queued")
+
+    def level3(self, c, d_sensor, hfov, foclen, fnum):
+        """-> (maps, any_valid), or None when a deferred-ray list overflowed (a caustic along the window edge): then the strict
+        psf_map level decides every ray"""
+        eb, st = self.eb, c.st
+        S, N, B, MS, f32, prov = c.S, c.N, c.B, _abi.MAX_SURF, torch.float32, self.prov
+        native = prov and c.native                          # both short levels native: the driver finishes the stack as well
         # [S,N,3] (the native edge driver computes them itself; the Python form is then only its check on the first stacks)
-        pobj = _object_points(lens, pts, hfov) if not edge_native or eb.get("pobj_checked", 0) < _HostFast.CHECKS else None
-        edge_done = False
-        if edge:
-            # ---- level 3, edge-exact: fast kernel (already running on provisional states, or launched here on the exact ones) + strict
-            # re-trace of the rays at the window edge + normalisation, no host wait in between
-            pred3 = counts.rows[keys[2]]
-            h = st.h_par[2]
-            hn = h.numpy()
-            if eb.get("pred_ref") is not pred3:                 # the table's rows are replaced, never edited: same object = same counts
-                hn[B + S * N * 3:B + S * N * 3 + B * 2 * MS].reshape(B, 2, MS)[:] = pred3
-                eb["pred_ref"] = pred3
-            par = st.d_par[2]
-            if edge_native:
-                # object points, uploads, re-trace, normalisation, counts back: one call (csrc/stack_host.cpp: aadff_edge_finish)
-                pupils_ready.result()
-                pn = eb.get("pts_np")
-                if pn is None or eb.get("pts_np_key") != (float(depth_plane_mm), grid):
-                    pn = eb["pts_np"] = np.ascontiguousarray(pts.numpy(), dtype=np.float32)
-                    eb["pts_np_key"] = (float(depth_plane_mm), grid)
-                hf64, ds32 = np.asarray(hfov, dtype=np.float64), np.asarray(d_sensor, dtype=np.float32)
-                rc = lib.aadff_edge_finish(C.byref(edge_struct()), C.c_void_p(pn.ctypes.data), C.c_void_p(hf64.ctypes.data), C.c_void_p(ds32.ctypes.data),
-                                           float(np.float32(lens.r_last)), float(np.float32(lens.sensor_size[1])), float(np.float32(lens.sensor_size[0])),
-                                           _abi.ptr(centre), _abi.ptr(maps), sp, C.c_void_p(eb["uploaded"].cuda_event), C.c_void_p(eb["done"].cuda_event))
-                if rc != 0:
-                    raise RuntimeError("aadff_edge_finish failed: " + lib.aadff_last_error().decode(errors="replace"))
-                eb["busy"] = True
-                if pobj is not None:                                               # the driver's object points against the reference's tensor operations
-                    eb["pobj_checked"] = eb.get("pobj_checked", 0) + 1
-                    if not torch.equal(h[B:B + S * N * 3].view(f32).view(S, N, 3).view(torch.int32), pobj.view(torch.int32)):
-                        _HostNative.switch_off("psf_diff's object points")
-                mark("level 3 inputs")
-            else:
-                hn[:B].view(np.float32)[:] = np.repeat(np.asarray(d_sensor, dtype=np.float32), L)
-                h[B:B + S * N * 3].view(f32).view(S, N, 3).copy_(pobj)
-            if edge_native:
-                pass
-            elif prov:
+        pobj = c.object_points(hfov) if not native or eb.get("pobj_checked", 0) < _HostFast.CHECKS else None
+        pred3 = c.counts.rows[c.keys[2]]
+        h = st.h_par[2]
+        if eb.get("pred_ref") is not pred3:                 # the table's rows are replaced, never edited: same object = same counts
+            h.numpy()[B + S * N * 3:B + S * N * 3 + B * 2 * MS].reshape(B, 2, MS)[:] = pred3
+            eb["pred_ref"] = pred3
+        if native:
+            # object points, uploads, re-trace, normalisation, counts back: one call (csrc/stack_host.cpp: aadff_edge_finish)
+            c.pupils_ready.result()
+            pn = eb.get("pts_np")
+            if pn is None or eb.get("pts_np_key") != (c.depth, c.grid):
+                pn = eb["pts_np"] = np.ascontiguousarray(c.pts.numpy(), dtype=np.float32)
+                eb["pts_np_key"] = (c.depth, c.grid)
+            hf64, ds32, lens = np.asarray(hfov, dtype=np.float64), np.asarray(d_sensor, dtype=np.float32), c.lens
+            _abi.call("aadff_edge_finish", C.byref(self._struct(c)), C.c_void_p(pn.ctypes.data), C.c_void_p(hf64.ctypes.data), C.c_void_p(ds32.ctypes.data),
+                      float(np.float32(lens.r_last)), float(np.float32(lens.sensor_size[1])), float(np.float32(lens.sensor_size[0])),
+                      _abi.ptr(self.centre), _abi.ptr(self.maps), c.sp, C.c_void_p(eb["uploaded"].cuda_event), C.c_void_p(eb["done"].cuda_event))
+            eb["busy"] = True
+            if pobj is not None:                                               # the driver's object points against the reference's tensor operations
+                eb["pobj_checked"] = eb.get("pobj_checked", 0) + 1
+                if not torch.equal(h[B:B + S * N * 3].view(f32).view(S, N, 3).view(torch.int32), pobj.view(torch.int32)):
+                    _HostNative.switch_off("psf_diff's object points")
+            c.mark("level 3 inputs")
+        else:
+            par, cnt = st.d_par[2], eb["count"]
+            h.numpy()[:B].view(np.float32)[:] = np.repeat(np.asarray(d_sensor, dtype=np.float32), c.L)
+            h[B:B + S * N * 3].view(f32).view(S, N, 3).copy_(pobj)
+            if prov:
                 eb["h_focus"][S:] = torch.tensor([float(np.tan(v)) for v in hfov], dtype=torch.float64).to(f32)
                 eb["d_focus"][S:].copy_(eb["h_focus"][S:], non_blocking=True)
             else:
                 # the S lens states as the fast kernel reads them (aadff_lens_state_t: 5 floats, 3 ints per state)
-                sw = hin.numpy()[:nst].reshape(S, nst // S)
+                nst = eb["nst"]
+                sw = eb["h_in"].numpy()[:nst].reshape(S, nst // S)
                 sf = sw.view(np.float32)
                 sf[:, 0], sf[:, 1], sf[:, 2] = d_sensor, hfov, [float(np.tan(v)) for v in hfov]
                 sf[:, 3], sf[:, 4] = foclen, fnum
                 sw[:, 5], sw[:, 6], sw[:, 7] = GEO_SPP, 0, 0
-                eb["d_in"][:nst].copy_(hin[:nst], non_blocking=True)
-                du.copy_(eb["h_u"], non_blocking=True)
+                eb["d_in"][:nst].copy_(eb["h_in"][:nst], non_blocking=True)
+                eb["d_u"].copy_(eb["h_u"], non_blocking=True)
                 cnt[B:].zero_()
-            if not edge_native:
-                pupils_ready.result()
-                par.copy_(h, non_blocking=True)
-                st.d_pupil[st.n_pf:st.n_pf + st.n_pm].copy_(hp[st.n_pf:st.n_pf + st.n_pm], non_blocking=True)
-                eb["uploaded"].record(stream)
-                eb["busy"] = True
-                mark("level 3 inputs")
-                if not prov:
-                    launch_edge(_ptr_at(eb["d_in"], 0), None)
-                _abi.call("aadff_strict_edge_retrace", _ptr_at(par, B), N, B, _abi.ptr(st.pset), _abi.ptr(tab_dev), len(wv), n_surf, _abi.ptr(st.bt_main),
-                          _ptr_at(par, 0), _ptr_at(st.d_pupil, st.n_pf), spp, _ptr_at(par, B + S * N * 3), float(lens.pixel_size), ks, _abi.ptr(centre),
-                          _ptr_at(cnt, 0), _abi.ptr(eb["list"]), EDGE_CAP, _abi.ptr(eb["raw"]), _ptr_at(cnt, B),
-                          _abi.ptr(eb["states_prov"]) if prov else None, _ptr_at(eb["d_focus"], S) if prov else None, _abi.ptr(eb["slope"]) if prov else None, sp)
-                _abi.call("aadff_psf_normalise", _abi.ptr(eb["raw"]), S, N, L, float(lens.pixel_size), ks, 1, _abi.ptr(maps), sp)
-                eb["h_back"].copy_(cnt, non_blocking=True)
-                eb["done"].record(stream)
-            yield eb["done"]
-            back = eb["h_back"].numpy()
-            bits = int(back[B])
-            counts.stats["edge"] = counts.stats.get("edge", 0) + 1
-            counts.stats["edge_rays"] = counts.stats.get("edge_rays", 0) + int(back[:B].sum())
-            lens._edge_last = {"rays": back[:B].copy(), "flags": bits}
-            mark("level 3 (edge) waited for")
-            if bits & 1:
-                raise FloatingPointError("found nan in ft in non-diff newton method.")
-            assert not bits & 2, "No sampled rays is valid."
-            if bits & 16:                                       # a list overflowed (a caustic along the window edge): the strict psf_map decides every ray
-                counts.stats["edge_overflows"] = counts.stats.get("edge_overflows", 0) + 1
-                if pobj is None:
-                    pobj = _object_points(lens, pts, hfov)
-                if vec is not None:
-                    _pupil_rows(vec, u, st.off_chief, st.off_chief + GEO_SPP, GEO_SPP, enp_rr * 0.5, enp_z, hp[st.n_pf + st.n_pm:])
-                else:
-                    hp[st.n_pf + st.n_pm:].view(S, L, GEO_SPP, 3).copy_(_pupil_points(uc[:, :, 0], uc[:, :, 1], enp_rr * 0.5, enp_z))
-                pupils_ready = concurrent.futures.Future()
-                pupils_ready.set_result(None)
-            else:
-                edge_done = True
-                any_valid = torch.ones(B, dtype=torch.int32)
-        if edge_done:
-            pass
-        elif fused:
-            pred3 = counts.rows[keys[2]]
-            maps = torch.empty((S, L, grid * ks, grid * ks), dtype=f32, device=dev)
-            centre = torch.empty((B, N, 2), dtype=f32, device=dev)
-            # two-variant jobs (aadff_strict_psf_points_alt): a batch whose CHIEF count at exactly one surface has been seen at two
-            # neighbouring values n, n + 1 (and nothing else undecided in its chief row) is rendered under both in this launch
-            # (not inside a StrictPipeline: there the re-launch runs beside the next stack's psf_map launch for free, while the second
-            # variant makes every launch 4.6 % longer - measured 3.63 against 3.97 ms per stack at depth 3)
-            alt = _two_variant_words(counts.seen[keys[2]][:, 0], curved) if ALT_JOBS and getattr(lens, "_strict_l3_chain", None) is None else None
-            if alt is not None and (alt >= 0).any():
-                pred3 = pred3.copy()
-                ab = np.nonzero(alt >= 0)[0]
-                pred3[ab, 0, alt[ab] & 0xff] = (alt[ab] >> 8) + 1
-                ak = ("alt", grid, ks)
-                if not hasattr(st, "_alt_out"):
-                    st._alt_out = {}
-                if ak not in st._alt_out:
-                    st._alt_out[ak] = (torch.empty((B, grid * ks, grid * ks), dtype=f32, device=dev), torch.empty((B, N, 2), dtype=f32, device=dev))
-                maps_alt, centre_alt = st._alt_out[ak]
-                counts.stats["alt_jobs"] = counts.stats.get("alt_jobs", 0) + len(ab)
-            else:
-                alt = None
-            h = st.h_par[2]
-            h[:B].view(f32).copy_(torch.tensor(d_sensor, dtype=f32).repeat_interleave(L))
-            h[B:B + S * N * 3].view(f32).view(S, N, 3).copy_(pobj)
-            h[B + S * N * 3:B + S * N * 3 + B * 2 * MS].view(B, 2, MS).copy_(torch.from_numpy(pred3))
-            if alt is not None:
-                h[B + S * N * 3 + B * 2 * MS:].copy_(torch.from_numpy(alt))
-            n_up3 = h.numel() if alt is not None else h.numel() - B
+            c.pupils_ready.result()
+            par.copy_(h, non_blocking=True)
+            st.d_pupil[st.n_pf:st.n_pf + st.n_pm].copy_(c.hp[st.n_pf:st.n_pf + st.n_pm], non_blocking=True)
+            eb["uploaded"].record(c.stream)
+            eb["busy"] = True
+            c.mark("level 3 inputs")
+            if not prov:
+                self._launch(c, _ptr_at(eb["d_in"], 0), None)
+            _abi.call("aadff_strict_edge_retrace", _ptr_at(par, B), N, B, _abi.ptr(st.pset), _abi.ptr(c.tab_dev), len(c.wv), c.n_surf, _abi.ptr(st.bt_main),
+                      _ptr_at(par, 0), _ptr_at(st.d_pupil, st.n_pf), c.spp, _ptr_at(par, B + S * N * 3), float(c.lens.pixel_size), c.ks, _abi.ptr(self.centre),
+                      _ptr_at(cnt, 0), _abi.ptr(eb["list"]), EDGE_CAP, _abi.ptr(eb["raw"]), _ptr_at(cnt, B),
+                      _abi.ptr(eb["states_prov"]) if prov else None, _ptr_at(eb["d_focus"], S) if prov else None, _abi.ptr(eb["slope"]) if prov else None, c.sp)
+            _abi.call("aadff_psf_normalise", _abi.ptr(eb["raw"]), S, N, c.L, float(c.lens.pixel_size), c.ks, 1, _abi.ptr(self.maps), c.sp)
+            eb["h_back"].copy_(cnt, non_blocking=True)
+            eb["done"].record(c.stream)
+        yield eb["done"]
+        back = eb["h_back"].numpy()
+        bits = int(back[B])
+        c.counts.bump("edge")
+        c.counts.bump("edge_rays", int(back[:B].sum()))
+        c.lens._edge_last = {"rays": back[:B].copy(), "flags": bits}
+        c.mark("level 3 (edge) waited for")
+        _raise_if_nan(bits & 1)
+        assert not bits & 2, "No sampled rays is valid."
+        if bits & 16:
+            c.counts.bump("edge_overflows")
+            _host_pupils(c.vec, c.u, st.off_chief, c.uc, c.enp_rr * 0.5, c.enp_z, c.hp[st.n_pf + st.n_pm:])
+            return None
+        return self.maps, torch.ones(B, dtype=torch.int32)
 
-            def launch3(J, jobs_ptr, pred_ptr, res, on=None, alt_ptr=None):
-                # re-launches go to the short levels' stream: behind a pipeline's NEXT psf_map launch they would wait 3 ms (the host
-                # has seen the first launch finish, and waits for the re-launch before the convolution is queued: ordered either way)
-                par = st.d_par[2]
-                if alt_ptr is None:
-                    _abi.call("aadff_strict_psf_points", _ptr_at(par, B), N, J, jobs_ptr, _abi.ptr(st.pset), _abi.ptr(tab_dev), len(wv), n_surf,
-                              _abi.ptr(st.bt_main), _abi.ptr(st.bt_green), _ptr_at(par, 0), _ptr_at(st.d_pupil, st.n_pf), spp,
-                              _ptr_at(st.d_pupil, st.n_pf + st.n_pm), GEO_SPP, pred_ptr, float(lens.pixel_size), ks, grid, _abi.ptr(maps), _abi.ptr(centre),
-                              _ptr_at(res, 0), _ptr_at(res, J * 4 * MS), sp if on is None else on)
-                else:
-                    _abi.call("aadff_strict_psf_points_alt", _ptr_at(par, B), N, J, jobs_ptr, _abi.ptr(st.pset), _abi.ptr(tab_dev), len(wv), n_surf,
-                              _abi.ptr(st.bt_main), _abi.ptr(st.bt_green), _ptr_at(par, 0), _ptr_at(st.d_pupil, st.n_pf), spp,
-                              _ptr_at(st.d_pupil, st.n_pf + st.n_pm), GEO_SPP, pred_ptr, float(lens.pixel_size), ks, grid, _abi.ptr(maps), _abi.ptr(centre),
-                              _ptr_at(res, 0), _ptr_at(res, J * 4 * MS), alt_ptr, _abi.ptr(maps_alt), _abi.ptr(centre_alt),
-                              _ptr_at(res, J * 4 * MS + J), _ptr_at(res, J * 4 * MS + J + J * 2 * MS), sp if on is None else on)
 
-            pupils_ready.result()
-            st.d_pupil[st.n_pf:].copy_(hp[st.n_pf:], non_blocking=True)
-            mark("level 3 inputs")
-            chain = getattr(lens, "_strict_l3_chain", None)
-            if chain is not None and chain[0] is not None:
-                # StrictPipeline: behind the psf_map launch of the stack in front, not beside it - two such launches sharing the chip
-                # finish together, and the host would learn the first one's counts 3 ms later
-                stream.wait_event(chain[0])
-            n_dn3 = B * 4 * MS + B + (B * 2 * MS + B if alt is not None else 0)
-            ev3 = st.submit(2, n_up3, n_dn3, lambda par, res: launch3(B, None, _ptr_at(par, B + S * N * 3), res,
-                                                                          alt_ptr=None if alt is None else _ptr_at(par, B + S * N * 3 + B * 2 * MS)), stream)
-            if chain is not None:
-                chain[0] = ev3
-            yield ev3
-            r = st.result(2)
-            mark("level 3 launch waited for")
-            counts.stats["fused"] += 1
-            hb = r[:B * 4 * MS].view(np.uint32).reshape(B, 2, 2, MS)
-            any_valid = torch.from_numpy(r[B * 4 * MS:B * 4 * MS + B].copy())
-            ok2, fix = check_counts(hb[:, :, 0], pred3, curved, fwd_order)                        # [B,2]: chief and main of the batch
-            ok = ok2.all(-1)
-            if alt is not None:
-                # a two-variant batch whose run under n + 1 shows that the loop stops at n: the variant under n is the truth if ITS bits
-                # (bits_alt: the unchanged ones in front of the undecided surface, its own behind) confirm the rest of its row
-                o2 = B * 4 * MS + B
-                hb_alt = r[o2:o2 + B * 2 * MS].view(np.uint32).reshape(B, 2, MS)
-                av_alt = r[o2 + B * 2 * MS:o2 + B * 2 * MS + B]
-                counts.stats["alt_retraced_max"] = max(counts.stats.get("alt_retraced_max", 0), int(hb_alt[ab, 0, MS - 1].max()))
-                sa, nl_ = alt[ab] & 0xff, alt[ab] >> 8
-                cand = ~ok2[ab, 0] & ok2[ab, 1] & (fix[ab, 0, sa] == nl_) & (av_alt[ab] >= 0)
-                if cand.any():
-                    cb = ab[cand]
-                    rows_lo = pred3[cb, 0].copy()
-                    rows_lo[np.arange(len(cb)), alt[cb] & 0xff] = alt[cb] >> 8
-                    ok_lo, _ = check_counts(hb_alt[cb, 0], rows_lo, curved, fwd_order)
-                    take = cb[ok_lo]
-                    if len(take):
-                        if _nan_in_run(hb_alt[take, 1][:, None], rows_lo[ok_lo][:, None], curved):
-                            raise FloatingPointError("found nan in ft in non-diff newton method.")
-                        with torch.cuda.stream(stream):
-                            for b_ in take:                  # (a few 70 KB device copies in front of the convolution; the centres stay behind:
-                                maps.view(B, grid * ks, grid * ks)[int(b_)].copy_(maps_alt[int(b_)], non_blocking=True)   # nothing reads them)
-                        pred3[take, 0] = rows_lo[ok_lo]
-                        hb = hb.copy()
-                        hb[take, 0, 0] = hb_alt[take, 0]
-                        hb[take, 0, 1] = hb_alt[take, 1]
-                        any_valid[torch.from_numpy(take)] = torch.from_numpy((av_alt[take] > 0).astype(np.int32))
-                        ok = ok.copy()
-                        ok[take] = True
-                        counts.stats["alt_taken"] = counts.stats.get("alt_taken", 0) + len(take)
-            if _nan_in_run(hb[ok][:, :, 1], pred3[ok], curved):
-                raise FloatingPointError("found nan in ft in non-diff newton method.")
-            truth = pred3.copy()
-            bad = np.nonzero(~ok)[0]
-            counts.stats["replayed_batches"] += len(bad)
-            rnd = 0
-            while len(bad) and rnd < FUSED_ROUNDS:          # re-launch the mispredicted batches with their corrected rows
-                rnd += 1
-                J = len(bad)
-                rows = fix[bad] if rnd == 1 else rows_next
-                hr = st.h_par[3].numpy()
-                hr[:J] = bad
-                hr[B:B + J * 2 * MS] = rows.reshape(-1)
-                yield st.submit(3, B + J * 2 * MS, J * 4 * MS + J, lambda par, res: launch3(J, _ptr_at(par, 0), _ptr_at(par, B), res, sp12), s12)
-                r = st.result(3)
-                counts.stats["fused_replays"] += 1
-                jb = r[:J * 4 * MS].view(np.uint32).reshape(J, 2, 2, MS)
-                okj2, fixj = check_counts(jb[:, :, 0], rows, curved, fwd_order)
-                okj = okj2.all(-1)
-                if _nan_in_run(jb[okj][:, :, 1], rows[okj], curved):
-                    raise FloatingPointError("found nan in ft in non-diff newton method.")
-                truth[bad[okj]] = rows[okj]
-                any_valid[bad[okj]] = torch.from_numpy(r[J * 4 * MS:J * 4 * MS + J][okj].copy())
-                bad, rows_next = bad[~okj], fixj[~okj]
-            mark("counts checked, re-launches")
-            if len(bad):                                    # still unconfirmed: the per-surface form finds the counts itself
-                counts.stats["per_surface_replays"] += 1
-                sel = torch.from_numpy(bad).to(dev)
-                par = st.d_par[2]
-                psf, cnt, av = _level3_batched(lens, sel, par[B:B + S * N * 3].view(f32).view(S, N, 3), st.pset, st.d_pupil[st.n_pf + st.n_pm:].view(B, GEO_SPP, 3),
-                                               st.d_pupil[st.n_pf:st.n_pf + st.n_pm].view(B, spp, 3), par[:B].view(f32), st.bt_green[:B], st.bt_main, tabs,
-                                               len(wv), n_surf, N, spp, ks, dev)
-                maps.view(B, grid * ks, grid * ks)[sel] = _tile(psf, grid, ks)
-                truth[bad] = cnt
-                any_valid[bad] = av
-            counts.learn(keys[2], truth)
+def _level3_fused(c, d_sensor, hfov):
+    """level 3 on speculated counts: ONE psf_map launch for the stack, the batches whose counts it does not confirm re-launched with
+    corrected rows (FUSED_ROUNDS at most), what is still unconfirmed then in the per-surface form -> (maps, any_valid)"""
+    lens, st, counts, curved = c.lens, c.st, c.counts, c.curved
+    S, L, N, B, MS, grid, ks, f32 = c.S, c.L, c.N, c.B, _abi.MAX_SURF, c.grid, c.ks, torch.float32
+    pobj = c.object_points(hfov)
+    pred3 = counts.rows[c.keys[2]]
+    maps = torch.empty((S, L, grid * ks, grid * ks), dtype=f32, device=c.dev)
+    centre = torch.empty((B, N, 2), dtype=f32, device=c.dev)
+    chain = getattr(lens, "_strict_l3_chain", None)
+    # two-variant jobs (aadff_strict_psf_points_alt): a batch whose CHIEF count at exactly one surface has been seen at two
+    # neighbouring values n, n + 1 (and nothing else undecided in its chief row) is rendered under both in this launch
+    # (not inside a StrictPipeline: there the re-launch runs beside the next stack's psf_map launch for free, while the second
+    # variant makes every launch 4.6 % longer - measured 3.63 against 3.97 ms per stack at depth 3)
+    alt = _two_variant_words(counts.seen[c.keys[2]][:, 0], curved) if ALT_JOBS and chain is None else None
+    if alt is not None and (alt >= 0).any():
+        pred3 = pred3.copy()
+        ab = np.nonzero(alt >= 0)[0]
+        pred3[ab, 0, alt[ab] & 0xff] = (alt[ab] >> 8) + 1
+        if (grid, ks) not in st.alt_out:
+            st.alt_out[grid, ks] = (torch.empty((B, grid * ks, grid * ks), dtype=f32, device=c.dev), torch.empty((B, N, 2), dtype=f32, device=c.dev))
+        maps_alt, centre_alt = st.alt_out[grid, ks]
+        counts.bump("alt_jobs", len(ab))
+    else:
+        alt = None
+    h = st.h_par[2]
+    h[:B].view(f32).copy_(torch.tensor(d_sensor, dtype=f32).repeat_interleave(L))
+    h[B:B + S * N * 3].view(f32).view(S, N, 3).copy_(pobj)
+    h[B + S * N * 3:B + S * N * 3 + B * 2 * MS].view(B, 2, MS).copy_(torch.from_numpy(pred3))
+    if alt is not None:
+        h[B + S * N * 3 + B * 2 * MS:].copy_(torch.from_numpy(alt))
+    n_up3 = h.numel() if alt is not None else h.numel() - B
+
+    def launch3(J, jobs_ptr, pred_ptr, res, on, alt_ptr=None):
+        par = st.d_par[2]
+        args = (_ptr_at(par, B), N, J, jobs_ptr, _abi.ptr(st.pset), _abi.ptr(c.tab_dev), len(c.wv), c.n_surf, _abi.ptr(st.bt_main), _abi.ptr(st.bt_green),
+                _ptr_at(par, 0), _ptr_at(st.d_pupil, st.n_pf), c.spp, _ptr_at(st.d_pupil, st.n_pf + st.n_pm), GEO_SPP, pred_ptr, float(lens.pixel_size),
+                ks, grid, _abi.ptr(maps), _abi.ptr(centre), _ptr_at(res, 0), _ptr_at(res, J * 4 * MS))
+        if alt_ptr is None:
+            _abi.call("aadff_strict_psf_points", *args, on)
         else:
-            points = pobj.to(dev).contiguous()
-            pm = _pupil_points(um[:, :, 0], um[:, :, 1], enp_rr, enp_z).reshape(B, spp, 3).to(dev).contiguous()
-            pc = _pupil_points(uc[:, :, 0], uc[:, :, 1], enp_rr * 0.5, enp_z).reshape(B, GEO_SPP, 3).to(dev).contiguous()
-            pset = torch.arange(S, dtype=torch.int32).repeat_interleave(L).to(dev)
-            zs = torch.tensor(d_sensor, dtype=f32).repeat_interleave(L).to(dev)
-            bt_main = torch.arange(L, dtype=torch.int32).repeat(S).to(dev)
-            mark("level 3 inputs")
-            psf, cnt, any_valid = _level3_batched(lens, None, points, pset, pc, pm, zs, bt_green, bt_main, tabs, len(wv), n_surf, N, spp, ks, dev)
-            counts.learn(keys[2], cnt)
-            counts.stats["seeded"] += 1
-            maps = _tile(psf, grid, ks).reshape(S, L, grid * ks, grid * ks)
-        mark("level 3 done")
-        if marks is not None:
-            lens._strict_timing = [("draws and setup", round((marks[0][1] - t_enter) * 1e3, 3))] + [(b[0], round((b[1] - a[1]) * 1e3, 3)) for a, b in zip(marks, marks[1:])]
-    assert bool(any_valid.bool().all()), "No sampled rays is valid."
-    if phase == "psf":
-        return maps
-    # the lens is left focused at the last distance
-    lens._state_sync()
-    hs = lens._state_host
-    hs.d_sensor, hs.hfov, hs.tan_hfov = float(d_sensor[-1]), float(hfov[-1]), float(np.tan(hfov[-1]))
-    hs.foclen, hs.fnum = float(foclen[-1]), float(fnum[-1])
-    if lens._state_dev is not None:
-        lens._state_upload()
-    lens._strict_stack_scalars = {"d_sensor": d_sensor, "hfov": hfov}
-    return maps
+            _abi.call("aadff_strict_psf_points_alt", *args, alt_ptr, _abi.ptr(maps_alt), _abi.ptr(centre_alt), _ptr_at(res, J * 4 * MS + J),
+                      _ptr_at(res, J * 4 * MS + J + J * 2 * MS), on)
+
+    c.pupils_ready.result()
+    st.d_pupil[st.n_pf:].copy_(c.hp[st.n_pf:], non_blocking=True)
+    c.mark("level 3 inputs")
+    if chain is not None and chain[0] is not None:
+        # StrictPipeline: behind the psf_map launch of the stack in front, not beside it - two such launches sharing the chip
+        # finish together, and the host would learn the first one's counts 3 ms later
+        c.stream.wait_event(chain[0])
+    n_dn3 = B * 4 * MS + B + (B * 2 * MS + B if alt is not None else 0)
+    ev3 = st.submit(2, n_up3, n_dn3, lambda par, res: launch3(B, None, _ptr_at(par, B + S * N * 3), res, c.sp,
+                                                              None if alt is None else _ptr_at(par, B + S * N * 3 + B * 2 * MS)), c.stream)
+    if chain is not None:
+        chain[0] = ev3
+    yield ev3
+    r = st.result(2)
+    c.mark("level 3 launch waited for")
+    counts.bump("fused")
+    hb = r[:B * 4 * MS].view(np.uint32).reshape(B, 2, 2, MS)
+    any_valid = torch.from_numpy(r[B * 4 * MS:B * 4 * MS + B].copy())
+    ok2, fix = check_counts(hb[:, :, 0], pred3, curved, c.fwd_order)                        # [B,2]: chief and main of the batch
+    ok = ok2.all(-1)
+    if alt is not None:
+        hb, ok = _adopt_two_variant(c, r, alt, pred3, hb, ok, ok2, fix, any_valid, maps, maps_alt)
+    _raise_if_nan(_nan_in_run(hb[ok][:, :, 1], pred3[ok], curved))
+    truth = pred3.copy()
+    bad = np.nonzero(~ok)[0]
+    counts.bump("replayed_batches", len(bad))
+    rnd = 0
+    while len(bad) and rnd < FUSED_ROUNDS:          # re-launch the mispredicted batches with their corrected rows
+        rnd += 1
+        J = len(bad)
+        rows = fix[bad] if rnd == 1 else rows_next
+        hr = st.h_par[3].numpy()
+        hr[:J] = bad
+        hr[B:B + J * 2 * MS] = rows.reshape(-1)
+        # (re-launches go to the short levels' stream: behind a pipeline's NEXT psf_map launch they would wait 3 ms - the host has
+        # seen the first launch finish, and waits for the re-launch before the convolution is queued: ordered either way)
+        yield st.submit(3, B + J * 2 * MS, J * 4 * MS + J, lambda par, res: launch3(J, _ptr_at(par, 0), _ptr_at(par, B), res, c.sp12), c.s12)
+        r = st.result(3)
+        counts.bump("fused_replays")
+        jb = r[:J * 4 * MS].view(np.uint32).reshape(J, 2, 2, MS)
+        okj2, fixj = check_counts(jb[:, :, 0], rows, curved, c.fwd_order)
+        okj = okj2.all(-1)
+        _raise_if_nan(_nan_in_run(jb[okj][:, :, 1], rows[okj], curved))
+        truth[bad[okj]] = rows[okj]
+        any_valid[bad[okj]] = torch.from_numpy(r[J * 4 * MS:J * 4 * MS + J][okj].copy())
+        bad, rows_next = bad[~okj], fixj[~okj]
+    c.mark("counts checked, re-launches")
+    if len(bad):                                    # still unconfirmed: the per-surface form finds the counts itself
+        counts.bump("per_surface_replays")
+        sel = torch.from_numpy(bad).to(c.dev)
+        par = st.d_par[2]
+        psf, cnt, av = _level3_batched(lens, sel, par[B:B + S * N * 3].view(f32).view(S, N, 3), st.pset, st.d_pupil[st.n_pf + st.n_pm:].view(B, GEO_SPP, 3),
+                                       st.d_pupil[st.n_pf:st.n_pf + st.n_pm].view(B, c.spp, 3), par[:B].view(f32), st.bt_green[:B], st.bt_main, c.tabs,
+                                       len(c.wv), c.n_surf, N, c.spp, ks, c.dev)
+        maps.view(B, grid * ks, grid * ks)[sel] = _tile(psf, grid, ks)
+        truth[bad] = cnt
+        any_valid[bad] = av
+    counts.learn(c.keys[2], truth)
+    return maps, any_valid
+
+
+def _adopt_two_variant(c, r, alt, pred3, hb, ok, ok2, fix, any_valid, maps, maps_alt):
+    """A two-variant batch whose run under n + 1 shows that the loop stops at n: the variant under n is the truth if ITS bits
+    (bits_alt: the unchanged ones in front of the undecided surface, its own behind) confirm the rest of its row.  Such batches
+    are taken into maps, pred3 and any_valid; returns (hb, ok) with them confirmed."""
+    B, MS, curved, counts = c.B, _abi.MAX_SURF, c.curved, c.counts
+    ab = np.nonzero(alt >= 0)[0]
+    o2 = B * 4 * MS + B
+    hb_alt = r[o2:o2 + B * 2 * MS].view(np.uint32).reshape(B, 2, MS)
+    av_alt = r[o2 + B * 2 * MS:o2 + B * 2 * MS + B]
+    counts.stats["alt_retraced_max"] = max(counts.stats.get("alt_retraced_max", 0), int(hb_alt[ab, 0, MS - 1].max()))
+    sa, n_lo = alt[ab] & 0xff, alt[ab] >> 8
+    cand = ~ok2[ab, 0] & ok2[ab, 1] & (fix[ab, 0, sa] == n_lo) & (av_alt[ab] >= 0)
+    if not cand.any():
+        return hb, ok
+    cb = ab[cand]
+    rows_lo = pred3[cb, 0].copy()
+    rows_lo[np.arange(len(cb)), alt[cb] & 0xff] = alt[cb] >> 8
+    ok_lo, _ = check_counts(hb_alt[cb, 0], rows_lo, curved, c.fwd_order)
+    take = cb[ok_lo]
+    if not len(take):
+        return hb, ok
+    _raise_if_nan(_nan_in_run(hb_alt[take, 1][:, None], rows_lo[ok_lo][:, None], curved))
+    side = c.grid * c.ks
+    with torch.cuda.stream(c.stream):
+        for b in take:                                  # (a few 70 KB device copies in front of the convolution; the centres stay
+            maps.view(B, side, side)[int(b)].copy_(maps_alt[int(b)], non_blocking=True)        # behind: nothing reads them)
+    pred3[take, 0] = rows_lo[ok_lo]
+    hb = hb.copy()
+    hb[take, 0, 0] = hb_alt[take, 0]
+    hb[take, 0, 1] = hb_alt[take, 1]
+    any_valid[torch.from_numpy(take)] = torch.from_numpy((av_alt[take] > 0).astype(np.int32))
+    ok = ok.copy()
+    ok[take] = True
+    counts.bump("alt_taken", len(take))
+    return hb, ok
+
+
+def _level3_seed(c, d_sensor, hfov):
+    """the round-4 form of level 3 (the seed run: no count table yet) -> (maps, any_valid)"""
+    S, L, B, spp, dev, f32 = c.S, c.L, c.B, c.spp, c.dev, torch.float32
+    points = c.object_points(hfov).to(dev).contiguous()
+    pm = _pupil_points(c.um[:, :, 0], c.um[:, :, 1], c.enp_rr, c.enp_z).reshape(B, spp, 3).to(dev).contiguous()
+    pc = _pupil_points(c.uc[:, :, 0], c.uc[:, :, 1], c.enp_rr * 0.5, c.enp_z).reshape(B, GEO_SPP, 3).to(dev).contiguous()
+    pset = torch.arange(S, dtype=torch.int32).repeat_interleave(L).to(dev)
+    zs = torch.tensor(d_sensor, dtype=f32).repeat_interleave(L).to(dev)
+    bt_main = torch.arange(L, dtype=torch.int32).repeat(S).to(dev)
+    c.mark("level 3 inputs")
+    psf, cnt, any_valid = _level3_batched(c.lens, None, points, pset, pc, pm, zs, c.bt_green, bt_main, c.tabs, len(c.wv), c.n_surf, c.N, spp, c.ks, dev)
+    c.counts.learn(c.keys[2], cnt)
+    c.counts.bump("seeded")
+    return _tile(psf, c.grid, c.ks).reshape(S, L, c.grid * c.ks, c.grid * c.ks), any_valid
+
 
 
 class StrictPipeline:
