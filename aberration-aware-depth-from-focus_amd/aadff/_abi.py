@@ -104,6 +104,7 @@ PROTOTYPES = {
     "aadff_strict_centroid": [_P, _P, _I, _I, _I, _P, _P, _P],
     "aadff_trace_points": [_P, _I, _P, _P, _I, _F, _F, _P, _I, _P, _P, _P, _P, _P],
     "aadff_psf_splat": [_P, _P, _P, _I, _I, _F, _I, _P, _P, _P],
+    "aadff_spot_moments": [_P, _I, _P, _I, _I, _I, _P, _I, _F, _F, _P, _I, _I, _P, _P, _P],
     "aadff_psf_points": [_P, _I, _I, _I, _P, _P, LensConst, _P, _P, _I, _L, _L, _P, _I, _L, _L, _I, _I, _I, _P, _P, _P, _P],
     "aadff_psf_points_staged": [_P, _I, _I, _I, _P, _P, LensConst, _P, _P, _I, _L, _L, _P, _I, _L, _L, _I, _I, _I, _P, _P, _P,
                                 C.POINTER(Stage), _P],

@@ -1361,6 +1361,99 @@ __global__ __launch_bounds__(NT) void refocus_kernel(const float* __restrict__ d
     }
 }
 
+// ------------------------------------------------------------------------------------
+// Spot moments of the ray-traced lens analysis: stratified pupil samples (deeplens/optics.py:539-591) from an object
+// point grid (sample_point_source :400-454), traced and projected to d_sensor, reduced per field point - the rays are never
+// stored.  One workgroup per field point runs every pass (wavelength) of that point in order, so pass 0's centroid stays in
+// LDS as the green reference of analysis_rms (:1975-2012); each lane keeps its hits in registers for the second phase.
+// Reductions run in a fixed order (wave butterfly, then waves 0..3), so a launch is bit-reproducible.
+// ------------------------------------------------------------------------------------
+constexpr int kSpotThreads = 256, kSpotWaves = kSpotThreads / 64;
+constexpr int kSpotMaxPairs = 4;          // two rays per lane: spp <= 2 * 256 * 4 = 2048 (analysis_rms: GEO_SPP)
+
+__global__ __launch_bounds__(kSpotThreads) void spot_moments_kernel(const float* __restrict__ points, int P, const float* __restrict__ u,
+                                                                    int spp, int num_angle, int n_pass,
+                                                                    const aadff_surface_t* __restrict__ surf, int n_surf, float pupil_z,
+                                                                    float r2_step, const aadff_lens_state_t* __restrict__ state, int ref_mode,
+                                                                    int want_s2, float4* __restrict__ moments, int* flags) {
+    __shared__ float red[3 * kSpotWaves];
+    __shared__ float centre[2];
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const float d_sensor = fresh_uniform(&state->d_sensor);
+    const float px = points[3 * p], py = points[3 * p + 1], pz = points[3 * p + 2];
+    const int rings = spp / num_angle;
+    const float inv_a = 1.f / (float)num_angle;
+    const int n_iter = (spp + 2 * kSpotThreads - 1) / (2 * kSpotThreads);
+    int nan_flag = 0;
+    for (int q = 0; q < n_pass; ++q) {
+        const float* uq = u + (size_t)q * 2 * spp * P;
+        const aadff_surface_t* tab = surf + (size_t)q * n_surf;
+        f2 hx[kSpotMaxPairs], hy[kSpotMaxPairs];
+        i2 ok[kSpotMaxPairs];
+#pragma unroll
+        for (int k = 0; k < kSpotMaxPairs; ++k) { hx[k] = hy[k] = f2s(0.f); ok[k] = (i2){0, 0}; }
+        float sx = 0.f, sy = 0.f, sn = 0.f;
+#pragma unroll 1
+        for (int k = 0; k < n_iter; ++k) {
+            const int s0 = tid + k * 2 * kSpotThreads;
+            if (s0 >= spp) break;
+            const int s1 = s0 + kSpotThreads;
+            const i2 act = {-1, s1 < spp ? -1 : 0};
+            const int sb = act.y ? s1 : s0;
+            // sample s = i * (spp / A) + j: sector i, ring j; theta block then r^2 block of P draws each (optics.py:571-582)
+            const int i0 = s0 / rings, ib = sb / rings;
+            const f2 ut = {uq[(size_t)(2 * s0) * P + p], uq[(size_t)(2 * sb) * P + p]};
+            const f2 ur = {uq[(size_t)(2 * s0 + 1) * P + p], uq[(size_t)(2 * sb + 1) * P + p]};
+            const f2 rev = (ut + (f2){(float)i0, (float)ib}) * inv_a;                       // theta / (2 pi)
+            const f2 rr = vsqrt((ur + (f2){(float)(s0 - i0 * rings), (float)(sb - ib * rings)}) * r2_step);
+            const f2 x2 = rr * (f2){__builtin_amdgcn_cosf(rev.x), __builtin_amdgcn_cosf(rev.y)};
+            const f2 y2 = rr * (f2){__builtin_amdgcn_sinf(rev.x), __builtin_amdgcn_sinf(rev.y)};
+            const Ray2 r = trace_pair_to_sensor(px, py, pz, x2, y2, pupil_z, act, tab, n_surf, d_sensor, nan_flag);
+            const f2 wx = vsel(r.alive, r.ox, f2s(0.f)), wy = vsel(r.alive, r.oy, f2s(0.f));
+            sx += wx.x + wx.y; sy += wy.x + wy.y;
+            sn += (r.alive.x ? 1.f : 0.f) + (r.alive.y ? 1.f : 0.f);
+#pragma unroll
+            for (int kk = 0; kk < kSpotMaxPairs; ++kk)       // constant register indices (a runtime index would spill to scratch)
+                if (kk == k) { hx[kk] = wx; hy[kk] = wy; ok[kk] = r.alive; }
+        }
+        sx = wave_sum(sx); sy = wave_sum(sy); sn = wave_sum(sn);
+        if ((tid & 63) == 0) { red[(tid >> 6) * 3] = sx; red[(tid >> 6) * 3 + 1] = sy; red[(tid >> 6) * 3 + 2] = sn; }
+        __syncthreads();
+        if (tid == 0) {
+            sx = sy = sn = 0.f;
+            for (int w = 0; w < kSpotWaves; ++w) { sx += red[3 * w]; sy += red[3 * w + 1]; sn += red[3 * w + 2]; }
+            if (!ref_mode || q == 0) {           // optics.py:1987,1997: the centroid divides by count + 0.0001
+                centre[0] = sx / (sn + 1e-4f);
+                centre[1] = sy / (sn + 1e-4f);
+            }
+        }
+        __syncthreads();
+        float s2 = 0.f;
+        if (want_s2) {
+            // wave-uniform, so in SGPRs: a VGPR pair {cx, cy} would make the compiler read cy through op_sel from its high half
+            // (the packed form tools/check_isa.py refuses)
+            const float cx = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, centre[0])));
+            const float cy = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, centre[1])));
+#pragma unroll
+            for (int k = 0; k < kSpotMaxPairs; ++k) {
+                const f2 dx = hx[k] - cx, dy = hy[k] - cy;
+                const f2 e = vsel(ok[k], dx * dx + dy * dy, f2s(0.f));
+                s2 += e.x + e.y;
+            }
+            s2 = wave_sum(s2);
+            if ((tid & 63) == 0) red[tid >> 6] = s2;
+            __syncthreads();
+            if (tid == 0) {
+                s2 = 0.f;
+                for (int w = 0; w < kSpotWaves; ++w) s2 += red[w];
+            }
+        }
+        if (tid == 0) moments[(size_t)q * P + p] = make_float4(sn, sx, sy, s2);
+        __syncthreads();                          // red / centre are rewritten by the next pass
+    }
+    if (nan_flag && flags) atomicOr(flags, 1);    // found nan in ft in non-diff newton method (surfaces.py:555-558)
+}
+
 }  // namespace aadff
 
 using namespace aadff;
@@ -1595,6 +1688,25 @@ int aadff_publish_flags(const int* flags_dev, int* mirror_host, aadff_stream_t s
         AADFF_CHECK_ARG(false, "publish_flags: mirror_host is not pinned (device-mapped) host memory");
     }
     hipLaunchKernelGGL(publish_flags_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, flags_dev, reinterpret_cast<int*>(mapped));
+    AADFF_CHECK_LAUNCH();
+    return 0;
+}
+
+int aadff_spot_moments(const float* points, int P, const float* u, int spp, int num_angle, int n_pass, const aadff_surface_t* surf,
+                       int n_surf, float pupil_z, float pupil_r, const aadff_lens_state_t* state, int ref_mode, int want_s2,
+                       float* moments, int* flags_or_null, aadff_stream_t stream) {
+    AADFF_CHECK_ARG(points && u && surf && state && moments, "spot_moments: NULL pointer");
+    AADFF_CHECK_ARG(P > 0 && P <= (1 << 20) && n_pass > 0 && n_pass <= 16, "spot_moments: bad sizes P=%d n_pass=%d", P, n_pass);
+    AADFF_CHECK_ARG(n_surf > 0 && n_surf <= AADFF_MAX_SURF, "spot_moments: n_surf %d outside [1,%d]", n_surf, AADFF_MAX_SURF);
+    AADFF_CHECK_ARG(num_angle > 0 && spp > 0 && spp % num_angle == 0 && spp <= 2 * kSpotThreads * kSpotMaxPairs,
+                    "spot_moments: spp=%d must be a positive multiple of num_angle=%d and at most %d (stratified pupil samples only)",
+                    spp, num_angle, 2 * kSpotThreads * kSpotMaxPairs);
+    AADFF_CHECK_ARG(ref_mode == 0 || ref_mode == 1, "spot_moments: ref_mode %d is 0 or 1", ref_mode);
+    AADFF_CHECK_ARG(std::isfinite(pupil_z) && std::isfinite(pupil_r) && pupil_r >= 0.f, "spot_moments: bad pupil (z=%g, r=%g)",
+                    (double)pupil_z, (double)pupil_r);
+    const float r2_step = (float)((double)pupil_r * (double)pupil_r / spp * num_angle);     // pupilr**2 / spp * num_angle
+    hipLaunchKernelGGL(spot_moments_kernel, dim3(P), dim3(kSpotThreads), 0, (hipStream_t)stream, points, P, u, spp, num_angle, n_pass,
+                       surf, n_surf, pupil_z, r2_step, state, ref_mode, want_s2, reinterpret_cast<float4*>(moments), flags_or_null);
     AADFF_CHECK_LAUNCH();
     return 0;
 }

@@ -1,6 +1,8 @@
 """Lensgroup for the MI355X build: the reference's lens-as-PSF-generator API
 (deeplens/optics.py: psf* :887-1026, sample_from_points :457, trace* :598-714, refocus
-:1155, calc_fov :1187, pupils :1312-1403, read_lens_json :2045) on HIP kernels.
+:1155, calc_fov :1187, pupils :1312-1403, read_lens_json :2045) on HIP kernels, and its ray-traced
+analysis (sample_pupil :539, sample_point_source :400, calc_magnification3 :1221, analysis_rms :1975,
+draw_spot_diagram :1832).
 
 Design: the focus-dependent scalars (d_sensor, hfov, foclen, fnum) live in
 a 32-byte `aadff_lens_state_t` ON THE DEVICE; refocus / post_computation write it with a
@@ -605,6 +607,229 @@ class Lensgroup(DeepObj):
         ray, _, _ = self.trace(ray)
         return ray.propagate_to(depth)
 
+    # ------------------------------------------------------------------ ray-traced lens analysis (spot statistics)
+    @torch.no_grad()
+    def sample_pupil(self, res=(512, 512), spp=16, num_angle=8, pupilr=None, pupilz=None):
+        """[spp, H, W, 3] points on the pupil plane (reference: optics.py:539-591).  Stratified when spp % num_angle == 0 and
+        spp < 10000 (sample s = i * (spp / A) + j: sector i, ring j, one [1,H,W] draw for theta, then one for r^2), otherwise
+        a [spp,H,W] theta block, then an r^2 block.  The draws come from `self.sampler` as ONE flat block (the same stream as
+        the reference's per-call draws); the arithmetic is the reference's torch calls on tensors of the reference's shapes
+        (per sample in the stratified branch), so with a HostSampler lens the points are the bits the reference computes on
+        the same CPU - torch's float32 cos / sin are not the same bits on every CPU, nor across tensor shapes on all of them."""
+        H, W = res
+        if pupilr is None or pupilz is None:
+            pupilz, pupilr = self.entrance_pupil()
+        u = self.sampler.rand_block([2 * spp * H * W])
+        if spp % num_angle != 0 or spp >= 10000:
+            u = u.reshape(2, spp, H, W)
+            theta = u[0] * 2 * np.pi
+            r2 = u[1] * pupilr ** 2
+            r = torch.sqrt(r2)
+            x = r * torch.cos(theta)
+            y = r * torch.sin(theta)
+        else:
+            u = u.reshape(spp, 2, 1, H, W)
+            x, y = [], []
+            s = 0
+            for i in range(num_angle):
+                for j in range(spp // num_angle):
+                    delta_theta = u[s, 0] * 2 * np.pi / num_angle
+                    theta = delta_theta + i * 2 * np.pi / num_angle
+                    delta_r2 = u[s, 1] * pupilr ** 2 / spp * num_angle
+                    r2 = delta_r2 + j * pupilr ** 2 / spp * num_angle
+                    r = torch.sqrt(r2)
+                    x.append(r * torch.cos(theta))
+                    y.append(r * torch.sin(theta))
+                    s += 1
+            x = torch.cat(x, dim=0)
+            y = torch.cat(y, dim=0)
+        o = torch.stack((x, y, torch.full_like(x, pupilz)), -1)
+        return o.to(self._ray_device())
+
+    def _ray_device(self):
+        """where the rays of the analysis live: strict / edge lenses keep them on the host (the reference's arithmetic)"""
+        return torch.device("cpu") if self.parity != "fast" else self.device
+
+    def _point_grid(self, R, depth, M):
+        """[M, M, 3] object points of sample_point_source (optics.py:421-438), the reference's float32 expressions"""
+        if R is None:
+            R = self.surfaces[0].r
+        Rw = R * self.sensor_res[1] / self.sensor_res[0]
+        x, y = torch.meshgrid(torch.linspace(-1, 1, M), torch.linspace(1, -1, M), indexing="xy")
+        x = x * Rw
+        y = y * R
+        return torch.stack((x, y, torch.full_like(x, depth)), -1)
+
+    @torch.no_grad()
+    def sample_point_source(self, R=None, depth=-10.0, M=11, spp=16, fov=10.0, forward=True, pupil=True, wvln=DEFAULT_WAVE,
+                            importance_sampling=False):
+        """Rays [spp, M, M] from an M x M object grid (x over +-R*W/H, y over R..-R, at z = depth) through the entrance pupil
+        (reference: optics.py:400-454).  d is normalised here and again by Ray (basics.py:244), as in the reference."""
+        if R is None:
+            R = self.surfaces[0].r
+        Rw = R * self.sensor_res[1] / self.sensor_res[0]
+        x, y = torch.meshgrid(torch.linspace(-1, 1, M), torch.linspace(1, -1, M), indexing="xy")
+        if importance_sampling:
+            x = torch.sqrt(x.abs()) * x.sign()
+            y = torch.sqrt(y.abs()) * y.sign()
+        x = x * Rw
+        y = y * R
+        dev = self._ray_device()
+        o = torch.stack((x, y, torch.full_like(x, depth)), -1).to(dev)
+        o = o.unsqueeze(0).repeat(spp, 1, 1, 1)
+        if not pupil:
+            raise Exception("Cone sampling specified by fov has been abandoned. Use pupil sampling instead.")
+        d = self.sample_pupil(res=(M, M), spp=spp) - o
+        d = d / torch.linalg.vector_norm(d, ord=2, dim=-1, keepdim=True)
+        return Ray(o, d, wvln, device=dev)
+
+    def _spot_moments(self, points, depth_wvlns, spp, ref_mode, want_s2, num_angle=8):
+        """aadff_spot_moments: [n_pass, P, 4] = (valid count, sum x, sum y, S2) per pass and object point (points [P,3]).
+        Draws: one block of n_pass * 2 * spp * P uniforms from `self.sampler`, i.e. the reference's sample_pupil calls of the
+        n_pass sample_point_source calls in order.  Synchronises and raises the reference's Newton error."""
+        dev = self._gpu()
+        P, L = points.shape[0], len(depth_wvlns)
+        pupilz, pupilr = self.entrance_pupil()
+        st = self._state_device()
+        n_u = L * 2 * spp * P
+        if self.sampler.on_device:
+            u = self.sampler.rand_block([n_u]).to(dev)
+        else:
+            host = torch.empty(n_u, dtype=torch.float32, pin_memory=True)
+            u = self.sampler.rand_into(host).to(dev, non_blocking=True)
+        pts = _abi.f32c(points, dev)
+        mom = torch.empty((L, P, 4), dtype=torch.float32, device=dev)
+        with _abi.on_device(dev):
+            stream = torch.cuda.current_stream(dev)
+            _abi.call("aadff_spot_moments", _abi.ptr(pts), P, _abi.ptr(u), spp, num_angle, L, _abi.ptr(self._table(depth_wvlns)),
+                      len(self.surfaces), float(pupilz), float(pupilr), _abi.ptr(st), int(ref_mode), int(want_s2), _abi.ptr(mom),
+                      _abi.ptr(self._flags_device()), C.c_void_p(stream.cuda_stream))
+        out = mom.cpu()
+        self.check_flags()
+        return out
+
+    @torch.no_grad()
+    def calc_magnification3(self, depth):
+        """Magnification from a traced 21 x 21 object grid, 512 rays per point (reference: optics.py:1221-1256): object x
+        (grid flipped on both axes) over the centroid x of its image, mean over the NaN-free top-left 10 x 10 quadrant; the
+        pinhole scale when that is 0.  Fast lenses: one aadff_spot_moments launch; strict / edge: the composed trace."""
+        M, spp = 21, 512
+        R = -depth * np.tan(self.hfov) * 0.5
+        if self.parity != "fast":
+            return self._calc_magnification3_composed(depth)
+        o = self._point_grid(R, depth, M)
+        mom = self._spot_moments(o.reshape(-1, 3), [DEFAULT_WAVE], spp, 0, False)[0].reshape(M, M, 4)
+        x1 = torch.flip(o[..., :2], [0, 1])[..., 0]
+        x2 = mom[..., 1] / mom[..., 0].add(EPSILON)
+        return self._mag_from_x(x1, x2, depth)
+
+    def _mag_from_x(self, x1, x2, depth):
+        M = x1.shape[0]
+        mag_x = x1 / x2
+        tmp = mag_x[:M // 2, :M // 2]
+        mag = 1 / torch.mean(tmp[~tmp.isnan()]).item()
+        if mag == 0:
+            scale = -depth * np.tan(self.hfov) / self.r_last
+            return 1 / scale
+        return mag
+
+    def _calc_magnification3_composed(self, depth):
+        """calc_magnification3 as the reference computes it: sample_point_source -> trace -> project_to -> torch sums"""
+        M, spp = 21, 512
+        ray = self.sample_point_source(M=M, spp=spp, depth=depth, R=-depth * np.tan(self.hfov) * 0.5, pupil=True)
+        o1 = torch.flip(ray.o.detach()[..., :2], [1, 2])
+        ray, _, _ = self.trace(ray)
+        o2 = ray.project_to(self.d_sensor)
+        x1 = o1[0, :, :, 0].cpu()
+        x2 = (torch.sum(o2[..., 0] * ray.ra, axis=0) / torch.sum(ray.ra, axis=0).add(EPSILON)).cpu()
+        return self._mag_from_x(x1, x2, depth)
+
+    @torch.no_grad()
+    def calc_scale_ray(self, depth):
+        """1 / calc_magnification3(depth); a 1-D tensor of depths gives one call per depth (reference: optics.py:1294-1307)."""
+        if isinstance(depth, torch.Tensor) and len(depth.shape) == 1:
+            return torch.tensor([1 / self.calc_magnification3(d) for d in depth])
+        return 1 / self.calc_magnification3(depth)
+
+    @staticmethod
+    def _rms_from_moments(mom, H, ref):
+        """(rms_avg, on-axis, off-axis) from per-pass moments [n_pass, H*H, 4] (optics.py:2000-2011, float32): the mean over
+        passes of sqrt(sum S2 / sum count); the on-axis term takes S2 at field [H//2+1, H//2+1] over the count at [H//2, H//2]
+        (the reference's indices), the off-axis one both at [0, 0].  With ref, pass 0 is the green reference pass."""
+        mom = mom.float()
+        n, s2 = mom[..., 0], mom[..., 3]
+        on_num, on_den = (H // 2 + 1) * H + H // 2 + 1, (H // 2) * H + H // 2
+        rms, rms_on, rms_off = [], [], []
+        for w in range(1 if ref else 0, mom.shape[0]):
+            rms.append(torch.sqrt(torch.sum(s2[w]) / torch.sum(n[w])))
+            rms_on.append(torch.sqrt(s2[w, on_num] / n[w, on_den]))
+            rms_off.append(torch.sqrt(s2[w, 0] / n[w, 0]))
+        return sum(rms) / len(rms), sum(rms_on) / len(rms_on), sum(rms_off) / len(rms_off)
+
+    def analysis_rms(self, depth=DEPTH, ref=True):
+        """RMS spot radii (rms_avg, on-axis, off-axis) in mm, 0-dim tensors (reference: optics.py:1975-2012): calc_scale_ray,
+        then with `ref` a green pass whose per-field centroids are the reference of the R, G, B passes (else each pass its own
+        centroid), 31 x 31 fields x 2048 rays each.  Fast lenses: one aadff_spot_moments launch for all passes; strict / edge:
+        the reference's composed trace and torch reductions."""
+        H = 31
+        scale = self.calc_scale_ray(depth)
+        if self.parity != "fast":
+            return self._analysis_rms_composed(depth, ref, scale)
+        o = self._point_grid(self.sensor_size[0] / 2 * scale, depth, H)
+        wvlns = [DEFAULT_WAVE, *WAVE_RGB] if ref else list(WAVE_RGB)
+        mom = self._spot_moments(o.reshape(-1, 3), wvlns, GEO_SPP, int(ref), True)
+        return self._rms_from_moments(mom, H, ref)
+
+    def _analysis_rms_composed(self, depth=DEPTH, ref=True, scale=None):
+        """analysis_rms line by line (optics.py:1982-2011) on sample_point_source + trace + project_to"""
+        H = 31
+        if scale is None:
+            scale = self.calc_scale_ray(depth)
+        if ref:
+            ray = self.sample_point_source(M=H, spp=GEO_SPP, depth=depth, R=self.sensor_size[0] / 2 * scale, pupil=True, wvln=DEFAULT_WAVE)
+            ray, _, _ = self.trace(ray)
+            p_green = ray.project_to(self.d_sensor)
+            p_center_ref = (p_green * ray.ra.unsqueeze(-1)).sum(0) / ray.ra.sum(0).add(0.0001).unsqueeze(-1)
+        rms, rms_on_axis, rms_off_axis = [], [], []
+        for wvln in WAVE_RGB:
+            ray = self.sample_point_source(M=H, spp=GEO_SPP, depth=depth, R=self.sensor_size[0] / 2 * scale, pupil=True, wvln=wvln)
+            ray, _, _ = self.trace(ray)
+            o2 = ray.project_to(self.d_sensor)
+            o2_center = (o2 * ray.ra.unsqueeze(-1)).sum(0) / ray.ra.sum(0).add(0.0001).unsqueeze(-1)
+            o2_norm = (o2 - (p_center_ref if ref else o2_center)) * ray.ra.unsqueeze(-1)
+            rms.append(torch.sqrt(torch.sum(o2_norm ** 2 * ray.ra.unsqueeze(-1)) / torch.sum(ray.ra)))
+            rms_on_axis.append(torch.sqrt(torch.sum(o2_norm[:, H // 2 + 1, H // 2 + 1, :] ** 2 * ray.ra[:, H // 2 + 1, H // 2 + 1].unsqueeze(-1))
+                                          / torch.sum(ray.ra[:, H // 2, H // 2])))
+            rms_off_axis.append(torch.sqrt(torch.sum(o2_norm[:, 0, 0, :] ** 2 * ray.ra[:, 0, 0].unsqueeze(-1)) / torch.sum(ray.ra[:, 0, 0])))
+        return (sum(rms) / len(rms)).cpu(), (sum(rms_on_axis) / len(rms_on_axis)).cpu(), (sum(rms_off_axis) / len(rms_off_axis)).cpu()
+
+    @torch.no_grad()
+    def draw_spot_diagram(self, M=7, depth=DEPTH, wvln=DEFAULT_WAVE, save_name=None):
+        """M x M spot diagrams (1024 rays per field point, through trace2sensor) with their centroids, written with matplotlib
+        to `{save_name}_spot{-depth}mm.png` (reference: optics.py:1832-1862).  Returns the file name (None without matplotlib)."""
+        mag = self.calc_magnification3(depth)
+        ray = self.sample_point_source(M=M, R=self.sensor_size[0] / 2 / mag, depth=depth, wvln=wvln, spp=1024, pupil=True)
+        ray = self.trace2sensor(ray)
+        o2 = -ray.o.clone().cpu().numpy()
+        ra = ray.ra.clone().cpu().numpy()
+        save_name = f"./spot{-depth}mm.png" if save_name is None else f"{save_name}_spot{-depth}mm.png"
+        if plt is None:
+            logging.getLogger().info("draw_spot_diagram: matplotlib is not installed, %s not written", save_name)
+            return None
+        fig, axs = plt.subplots(M, M, figsize=(30, 30))
+        for i in range(M):
+            for j in range(M):
+                ra_ = ra[:, i, j]
+                x, y = o2[:, i, j, 0], o2[:, i, j, 1]
+                x, y = x[ra_ > 0], y[ra_ > 0]
+                xc, yc = x.sum() / ra_.sum(), y.sum() / ra_.sum()
+                axs[i, j].scatter(x, y, 1, "black")
+                axs[i, j].scatter([xc], [yc], None, "r", "x")
+                axs[i, j].set_aspect("equal", adjustable="datalim")
+        plt.savefig(save_name, bbox_inches="tight", format="png", dpi=300)
+        plt.close()
+        return save_name
+
     # ------------------------------------------------------------------ PSFs
     def point_source_grid(self, depth, grid=9, normalized=True, quater=False, center=False):
         """[grid,grid,3] field points, x in linspace(-.98,.98), y in linspace(.98,-.98)
@@ -835,16 +1060,21 @@ class Lensgroup(DeepObj):
     @torch.no_grad()
     def analysis(self, save_name="./test", render=False, multi_plot=False, plot_invalid=True, zmx_format=False, depth=DEPTH,
                  render_unwarp=False, lens_title=None):
-        """Reference signature (optics.py:1552).  Of its four products this build makes the one that comes off the hot path -
-        the PSF map picture (`draw_psf_map`, ks 51) - and logs the first-order numbers; the 2-D layout drawing, the RMS
-        spot statistics (they need `sample_point_source`) and the rendered resolution chart are outside the path (DESIGN.md
-        section 8) and are skipped with a log line instead of failing, so scripts that call `lens.analysis(...)` keep running."""
+        """Reference signature (optics.py:1552).  Of its four products this build makes the PSF map picture (`draw_psf_map`,
+        ks 51) and the RMS spot radii (`analysis_rms`, printed in the reference's words, optics.py:1561-1563), and logs the
+        first-order numbers; the 2-D layout drawing and the rendered resolution chart are outside the path (DESIGN.md
+        section 8) and are skipped with a log line instead of failing, so scripts that call `lens.analysis(...)` keep running.
+        Returns the PSF-map file name."""
         log = logging.getLogger()
         log.info("lens %s: foclen %.4f mm, F/%.4f, hfov %.5f rad, d_sensor %.5f mm, pixel %.6f mm",
                  getattr(self, "lens_name", "?"), self.foclen, self.fnum, self.hfov, self.d_sensor, self.pixel_size)
         out = self.draw_psf_map(save_name=save_name, ks=51, depth=depth)
-        log.info("PSF map written to %s; layout drawing, RMS spot analysis%s are not part of this build", out,
-                 " and chart rendering" if render else "")
+        rms_avg, rms_radius_on_axis, rms_radius_off_axis = self.analysis_rms()
+        line = (f"On-axis RMS radius: {round(rms_radius_on_axis.item() * 1000, 3)}um, Off-axis RMS radius: "
+                f"{round(rms_radius_off_axis.item() * 1000, 3)}um, Avg RMS spot size (radius): {round(rms_avg.item() * 1000, 3)}um.")
+        print(line)
+        log.info(line)
+        log.info("PSF map written to %s; layout drawing%s are not part of this build", out, " and chart rendering" if render else "")
         return out
 
 

@@ -303,6 +303,20 @@ int aadff_trace_points(const float* points_obj, int N, const float* u_theta, con
                        const aadff_lens_state_t* state, float* o_out, float* d_out, float* ra_out,
                        aadff_stream_t stream);
 
+/* Ray-traced lens analysis: per-field spot moments in one launch, the rays are never stored.  Stratified pupil samples
+ * (sample_pupil, deeplens/optics.py:539-591: sector i, ring j, theta = (u + i) 2 pi / A, r^2 = (u + j) R^2 A / spp) from
+ * the object points of sample_point_source (:400-454), traced through the lens and projected to the state's d_sensor
+ * (analysis_rms :1975-2012, calc_magnification3 :1221-1256).  points [P,3] (mm); u [n_pass][spp][2][P] raw uniform draws in
+ * the reference's order (per sample a theta block of P, then an r^2 block of P); surf [n_pass][n_surf] (one table per pass);
+ * pupil_z / pupil_r the entrance pupil; spp a multiple of num_angle, at most 2048.  One workgroup per field point runs the
+ * passes in order.  Out: moments [n_pass][P][4] = (valid count, sum x, sum y, S2 = sum ra |p - c|^2), c = sum / (count +
+ * 1e-4) of pass 0 (ref_mode 1) or of the pass itself (ref_mode 0); S2 = 0 when want_s2 = 0.  Fixed-order reductions (no
+ * float atomics): bit-reproducible.  flags bit 0: NaN in a Newton residual. */
+int aadff_spot_moments(const float* points, int P, const float* u, int spp, int num_angle, int n_pass,
+                       const aadff_surface_t* surf, int n_surf, float pupil_z, float pupil_r,
+                       const aadff_lens_state_t* state, int ref_mode, int want_s2, float* moments,
+                       int* flags_or_null, aadff_stream_t stream);
+
 /* Bilinear splat of sensor hits into ks x ks histograms + normalisation.  Replaces
  * forward_integral / assign_points_to_pixels, deeplens/monte_carlo.py:9-121 and the
  * division of deeplens/optics.py:978.  o [spp,N,3], ra [spp,N], centre [N,2];
