@@ -3,14 +3,16 @@
 `north_star` asks for the HIP kernels "through PyTorch-ROCm custom ops": each op below is a thin
 `torch.library.custom_op` wrapper (schema + fake/meta shape function) whose implementation packs pointers and calls
 libaadff.so on the current HIP stream.  With them the path is visible to FakeTensor / `torch.compile` tracing and
-`torch.library.opcheck`; no autograd formula is registered — the reference never back-propagates through these
-functions, so a backward through them raises torch's "not differentiable" error.
+`torch.library.opcheck`; no autograd formula is registered for them — the reference never back-propagates through these
+functions, so a backward through them raises torch's "not differentiable" error.  The differentiable
+forms of the image-space operators are separate ops (`render_psf_map_stack_diff`, `local_psf_render_diff`, at the end of
+the image-space section; public functions in aadff/diffrender.py): same forward kernels, backward in csrc/conv_bwd.hip.
 
 The deeplens mirror (deeplens/render_psf.py, deeplens/psfnet.py) calls these ops; the multi-launch planners
 (aadff/focal_stack.py, aadff/training.py) keep calling the ABI directly because they pass raw offsets into pinned rings.
 """
 import ctypes as C
-from typing import List
+from typing import List, Tuple
 
 import torch
 from torch.library import custom_op
@@ -102,6 +104,118 @@ def thinlens_render(img: torch.Tensor, depth: torch.Tensor, foc_dist: torch.Tens
 @thinlens_render.register_fake
 def _(img, depth, foc_dist, ks, foc_len, fnum, pixel_size, d_min, d_max):
     return torch.empty_like(img, dtype=torch.float32, memory_format=torch.contiguous_format)
+
+
+# ---------------------------------------------------------------- differentiable image space (csrc/conv_bwd.hip)
+# Plain (non-differentiable) ops over the backward ABI, and front ops whose forward is the EXISTING kernel and whose autograd
+# formula calls them.  A gradient that is not needed is not computed (NULL pointer) and comes back as an empty tensor.
+@custom_op("aadff::render_psf_map_stack_bwd", mutates_args=(), device_types="cuda")
+def render_psf_map_stack_bwd(img: torch.Tensor, psf_maps: torch.Tensor, dy: torch.Tensor, grid: int, need_img: bool,
+                             need_psf: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    B, Cn, H, W = img.shape
+    S, ks = psf_maps.shape[0], psf_maps.shape[2] // grid
+    x, p, g = img.contiguous().float(), psf_maps.contiguous().float(), dy.contiguous().float()
+    d_img = torch.empty_like(x) if need_img else x.new_empty((0,))
+    d_psf = torch.empty_like(p) if need_psf else x.new_empty((0,))
+    with torch.cuda.device(x.device):
+        ws, nbytes = None, C.c_size_t(0)
+        if need_psf:
+            _abi.call("aadff_render_psf_map_stack_bwd_workspace", B, Cn, S, H, W, grid, ks, C.byref(nbytes))
+            ws = torch.empty((max(1, (nbytes.value + 3) // 4),), dtype=torch.float32, device=x.device)
+        _abi.call("aadff_render_psf_map_stack_bwd", _abi.ptr(x), _abi.ptr(p), _abi.ptr(g), _abi.ptr(d_img) if need_img else None,
+                  _abi.ptr(d_psf) if need_psf else None, _abi.ptr(ws), C.c_size_t(nbytes.value), B, Cn, S, H, W, grid, ks, _st(x))
+    return d_img, d_psf
+
+
+@render_psf_map_stack_bwd.register_fake
+def _(img, psf_maps, dy, grid, need_img, need_psf):
+    return (torch.empty_like(img, dtype=torch.float32, memory_format=torch.contiguous_format) if need_img else img.new_empty((0,), dtype=torch.float32),
+            torch.empty_like(psf_maps, dtype=torch.float32, memory_format=torch.contiguous_format) if need_psf else img.new_empty((0,), dtype=torch.float32))
+
+
+@custom_op("aadff::local_psf_render_bwd", mutates_args=(), device_types="cuda")
+def local_psf_render_bwd(img: torch.Tensor, psf: torch.Tensor, dy: torch.Tensor, ks: int, need_img: bool,
+                         need_psf: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    B, Cn, H, W = img.shape
+    x, p, g = img.contiguous().float(), psf.contiguous().float(), dy.contiguous().float()
+    d_img = torch.empty_like(x) if need_img else x.new_empty((0,))
+    d_psf = torch.empty_like(p) if need_psf else x.new_empty((0,))
+    with torch.cuda.device(x.device):
+        _abi.call("aadff_local_psf_render_bwd", _abi.ptr(x), _abi.ptr(p), _abi.ptr(g), _abi.ptr(d_img) if need_img else None,
+                  _abi.ptr(d_psf) if need_psf else None, B, Cn, H, W, ks, _st(x))
+    return d_img, d_psf
+
+
+@local_psf_render_bwd.register_fake
+def _(img, psf, dy, ks, need_img, need_psf):
+    return (torch.empty_like(img, dtype=torch.float32, memory_format=torch.contiguous_format) if need_img else img.new_empty((0,), dtype=torch.float32),
+            torch.empty_like(psf, dtype=torch.float32, memory_format=torch.contiguous_format) if need_psf else img.new_empty((0,), dtype=torch.float32))
+
+
+@custom_op("aadff::render_psf_map_stack_diff", mutates_args=(), device_types="cuda")
+def render_psf_map_stack_diff(img: torch.Tensor, psf_maps: torch.Tensor, grid: int) -> torch.Tensor:
+    """render_psf_map_stack with an autograd formula (image and PSF maps); the forward is the same ABI call."""
+    B, Cn, H, W = img.shape
+    S, ks = psf_maps.shape[0], psf_maps.shape[2] // grid
+    x, p = img.contiguous().float(), psf_maps.contiguous().float()
+    out = torch.empty((B, Cn, S, H, W), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _abi.call("aadff_render_psf_map_stack", _abi.ptr(x), _abi.ptr(p), _abi.ptr(out), B, Cn, S, H, W, grid, ks, _st(x))
+    return out
+
+
+@render_psf_map_stack_diff.register_fake
+def _(img, psf_maps, grid):
+    B, Cn, H, W = img.shape
+    return img.new_empty((B, Cn, psf_maps.shape[0], H, W), dtype=torch.float32)
+
+
+def _map_setup(ctx, inputs, output):
+    img, psf_maps, grid = inputs
+    ctx.save_for_backward(img, psf_maps)
+    ctx.grid = grid
+
+
+def _map_backward(ctx, dy):
+    img, psf_maps = ctx.saved_tensors
+    need_img, need_psf = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    d_img, d_psf = torch.ops.aadff.render_psf_map_stack_bwd(img, psf_maps, dy, ctx.grid, need_img, need_psf)
+    return (d_img if need_img else None), (d_psf if need_psf else None), None
+
+
+render_psf_map_stack_diff.register_autograd(_map_backward, setup_context=_map_setup)
+
+
+@custom_op("aadff::local_psf_render_diff", mutates_args=(), device_types="cuda")
+def local_psf_render_diff(img: torch.Tensor, psf: torch.Tensor, ks: int) -> torch.Tensor:
+    """local_psf_render with an autograd formula (image and per-pixel PSFs); the forward is the same ABI call."""
+    B, Cn, H, W = img.shape
+    x, p = img.contiguous().float(), psf.contiguous().float()
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _abi.call("aadff_local_psf_render", _abi.ptr(x), _abi.ptr(p), _abi.ptr(out), B, Cn, H, W, ks, _st(x))
+    return out
+
+
+@local_psf_render_diff.register_fake
+def _(img, psf, ks):
+    return torch.empty_like(img, dtype=torch.float32, memory_format=torch.contiguous_format)
+
+
+def _local_setup(ctx, inputs, output):
+    img, psf, ks = inputs
+    ctx.save_for_backward(img, psf)
+    ctx.ks = ks
+
+
+def _local_backward(ctx, dy):
+    img, psf = ctx.saved_tensors
+    need_img, need_psf = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    d_img, d_psf = torch.ops.aadff.local_psf_render_bwd(img, psf, dy, ctx.ks, need_img, need_psf)
+    return (d_img if need_img else None), (d_psf if need_psf else None), None
+
+
+local_psf_render_diff.register_autograd(_local_backward, setup_context=_local_setup)
 
 
 # ---------------------------------------------------------------- PSF network (deeplens/psfnet.py:375-441)

@@ -22,44 +22,7 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-// ------------------------------------------------------------------------------------
-// Patch bounds: Python `int(i / grid * n)` in float64 (deeplens/render_psf.py:65-66).
-// Passed by value in the kernarg segment -> read with scalar loads.
-// ------------------------------------------------------------------------------------
-struct PatchBounds {
-    int hb[AADFF_MAX_GRID + 1];
-    int wb[AADFF_MAX_GRID + 1];
-    // ceil(2^32 / d) for the uniform block-index decompositions: n / d == __umulhi(n, magic) for
-    // n < 65536 (integer division has no scalar form on gfx950 and costs ~15 VALU slots each)
-    unsigned m_ntx, m_nty, m_nchunk, m_c;
-    // XCD-aware block order (xcd_remap): 1-D launches only.  gx, gy = logical grid extents; N = 8 xcd_q + xcd_r blocks (xcd_q = 0: plain order)
-    unsigned gx, gy, xcd_q, xcd_r, m_gx, m_gy;      // m_gx / m_gy != 0: magic multipliers, valid while the launch has < 65536 blocks
-};
-
-// Workgroups are dealt round-robin over the 8 XCDs (block b -> XCD b % 8; observed, not promised: speed only), each with an L2 of
-// its own.  Neighbouring bands share halo rows / columns (34 x 108 staged for 24 x 96 rendered: 1.6x), so with the plain order
-// every XCD's L2 fetches its halos from the fabric again (FETCH_SIZE 20 MB for a 12.6 MB image).  Remapped, XCD k works on the
-// k-th CONTIGUOUS eighth of the logical block order, whose neighbours then hit in that XCD's L2.
-// id = k + 8 j  ->  logical index start_k + j,  start_k = k q + min(k, r),  N = 8 q + r.
-__device__ __forceinline__ unsigned xcd_remap(unsigned id, unsigned q, unsigned r) {
-    const unsigned k = id & 7u, j = id >> 3;
-    return k * q + (k < r ? k : r) + j;
-}
-
-__host__ __device__ inline unsigned magic_of(unsigned d) { return (unsigned)((0x100000000ull + d - 1) / d); }
-__device__ __forceinline__ int udiv_magic(unsigned n, unsigned d, unsigned magic) { return d == 1 ? (int)n : (int)__umulhi(n, magic); }
-
-static void fill_bounds(int* b, int grid, int n) {
-    for (int i = 0; i <= grid; ++i) b[i] = (int)((double)i / (double)grid * (double)n);
-}
-
-__device__ __forceinline__ int reflect_idx(int i, int n) {
-    // torch 'reflect' padding (no edge repeat), then clamped: the clamp only matters for
-    // masked-out lanes of ragged tiles.
-    i = i < 0 ? -i : i;
-    i = i >= n ? 2 * n - 2 - i : i;
-    return min(max(i, 0), n - 1);
-}
+// PatchBounds, fill_bounds, the magic-multiplier divisions, xcd_remap and reflect_idx live in common.h (shared with conv_bwd.hip)
 
 // ------------------------------------------------------------------------------------
 // Fast path: one wave per 32x32 output tile of ONE patch and ONE channel plane.
@@ -1783,10 +1746,8 @@ static int launch_fast(const float* img, const float* psf, float* out, long sbc,
     return 0;
 }
 
-// out plane of (b, c, s) starts at out + (b*C + c)*sbc + s*ss (elements); the contiguous [B,C,S,H,W] stack is sbc = S*H*W, ss = H*W
-static int conv_dispatch(const float* img, const float* psf, float* out, long sbc, long ss, int B, int C, int S, int H, int W,
-                         int grid, int ks, hipStream_t st) {
-    AADFF_CHECK_ARG(img && psf && out, "render_psf_map: NULL pointer");
+// the shape domain of the patch convolution, shared by the forward entries and their backward (conv_bwd.hip)
+int conv_check_shape(int B, int C, int S, int H, int W, int grid, int ks) {
     AADFF_CHECK_ARG(B > 0 && C > 0 && S > 0 && H > 0 && W > 0, "render_psf_map: empty tensor (B=%d C=%d S=%d H=%d W=%d)", B, C, S, H, W);
     AADFF_CHECK_ARG(grid >= 1 && grid <= AADFF_MAX_GRID, "render_psf_map: grid %d outside [1,%d]", grid, AADFF_MAX_GRID);
     AADFF_CHECK_ARG(ks % 2 == 1, "PSF kernel size should be odd");
@@ -1794,6 +1755,14 @@ static int conv_dispatch(const float* img, const float* psf, float* out, long sb
     AADFF_CHECK_ARG(ks / 2 < H && ks / 2 < W, "render_psf_map: reflect padding %d needs H,W > pad", ks / 2);
     AADFF_CHECK_ARG(grid <= H && grid <= W, "render_psf_map: grid %d larger than image %dx%d", grid, H, W);
     AADFF_CHECK_ARG((size_t)B * C <= 65535, "render_psf_map: B*C too large");
+    return 0;
+}
+
+// out plane of (b, c, s) starts at out + (b*C + c)*sbc + s*ss (elements); the contiguous [B,C,S,H,W] stack is sbc = S*H*W, ss = H*W
+static int conv_dispatch(const float* img, const float* psf, float* out, long sbc, long ss, int B, int C, int S, int H, int W,
+                         int grid, int ks, hipStream_t st) {
+    AADFF_CHECK_ARG(img && psf && out, "render_psf_map: NULL pointer");
+    if (int rc = conv_check_shape(B, C, S, H, W, grid, ks)) return rc;
 
     PatchBounds pb;
     std::memset(&pb, 0, sizeof(pb));
@@ -2203,6 +2172,21 @@ __global__ __launch_bounds__(64) void local_psf_generic_kernel(const float* __re
 
 using namespace aadff;
 
+namespace aadff {
+// the shape domain of the per-pixel gather, shared with its backward (conv_bwd.hip)
+int local_check_shape(int B, int C, int H, int W, int ks) {
+    AADFF_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "local_psf_render: empty tensor");
+    AADFF_CHECK_ARG(ks % 2 == 1 && ks >= 1 && ks <= AADFF_MAX_KS, "local_psf_render: ks %d must be odd and <= %d", ks, AADFF_MAX_KS);
+    AADFF_CHECK_ARG(H <= 65535 && B <= 65535, "local_psf_render: H or B too large for the launch grid");
+    if (!(C <= LP_MAXC && (ks == 3 || ks == 5 || ks == 7 || ks == 9 || ks == 11 || ks == 13))) {       // generic kernel: PSFs and window in LDS
+        const int npx = ks <= 15 ? 64 : 16;
+        const size_t lds = ((size_t)npx * ks * ks + (size_t)C * ks * (npx + ks - 1)) * sizeof(float);
+        AADFF_CHECK_ARG(lds <= 160 * 1024, "local_psf_render: C=%d ks=%d needs %zu B of LDS", C, ks, lds);
+    }
+    return 0;
+}
+}  // namespace aadff
+
 extern "C" {
 
 int aadff_abi_version(void) { return AADFF_ABI_VERSION; }
@@ -2329,9 +2313,7 @@ int aadff_render_psf(const float* img, const float* psf, float* out, int B, int 
 int aadff_local_psf_render(const float* img, const float* psf, float* out, int B, int C, int H, int W, int ks,
                            aadff_stream_t stream) {
     AADFF_CHECK_ARG(img && psf && out, "local_psf_render: NULL pointer");
-    AADFF_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "local_psf_render: empty tensor");
-    AADFF_CHECK_ARG(ks % 2 == 1 && ks >= 1 && ks <= AADFF_MAX_KS, "local_psf_render: ks %d must be odd and <= %d", ks, AADFF_MAX_KS);
-    AADFF_CHECK_ARG(H <= 65535 && B <= 65535, "local_psf_render: H or B too large for the launch grid");
+    if (int rc = local_check_shape(B, C, H, W, ks)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (C <= LP_MAXC && (ks == 3 || ks == 5 || ks == 7 || ks == 9 || ks == 11 || ks == 13)) {
         dim3 g((W + LP_NPX - 1) / LP_NPX, H, B);
@@ -2354,7 +2336,6 @@ int aadff_local_psf_render(const float* img, const float* psf, float* out, int B
     } else {
         const int npx = ks <= 15 ? 64 : 16;
         const size_t lds = ((size_t)npx * ks * ks + (size_t)C * ks * (npx + ks - 1)) * sizeof(float);
-        AADFF_CHECK_ARG(lds <= 160 * 1024, "local_psf_render: C=%d ks=%d needs %zu B of LDS", C, ks, lds);
         dim3 g((W + npx - 1) / npx, H, B);
         if (npx == 64) {
             if (lds > 64 * 1024)

@@ -5,7 +5,8 @@ packs pointers for the C ABI.  Same four functions, argument order and assertion
 deeplens/render_psf.py (:12 render_psf, :31 render_psf_map, :76 local_psf_render, :110
 local_psf_render_high_res).  Inputs on any device are made contiguous fp32 on the GPU,
 outputs come back on the input's device.  Forward only: the reference never
-back-propagates through these, so tensors that require grad are refused.
+back-propagates through these (SURVEY.md §8b), so tensors that require grad are refused here;
+the differentiable forms of the same functions are in aadff/diffrender.py.
 """
 import numpy as np
 import torch
@@ -16,7 +17,7 @@ from aadff import ops as _ops      # noqa: F401  (registers torch.ops.aadff.*)
 
 def _prep(t, what):
     if t.requires_grad and torch.is_grad_enabled():
-        raise RuntimeError(f"{what}: forward-only HIP op, call it under torch.no_grad() or detach the input")
+        raise RuntimeError(f"{what}: forward-only HIP op, call it under torch.no_grad() or detach the input, or use aadff.diffrender.{what}")
     _abi.require_gpu()
     dev = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
     return dev

@@ -18,6 +18,8 @@
 #ifndef AADFF_H_
 #define AADFF_H_
 
+#include <stddef.h>   /* size_t */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -156,6 +158,32 @@ int aadff_render_psf(const float* img, const float* psf, float* out,
  * Replaces local_psf_render, deeplens/render_psf.py:76-107.  psf [B,H,W,ks,ks]. */
 int aadff_local_psf_render(const float* img, const float* psf, float* out,
                            int B, int C, int H, int W, int ks, aadff_stream_t stream);
+
+/* ---- backward of the image-space operators (csrc/conv_bwd.hip).  In the reference these functions are plain torch
+ * (F.pad + F.conv2d, unfold / fold) and torch.autograd differentiates them; the entries below are those gradients as
+ * closed forms.  Plain fp32 operands, fp32 accumulation, every sum in a fixed order (no float atomics): bitwise
+ * reproducible from run to run.  A gradient whose output pointer is NULL is not computed; both NULL is an error.
+ * The argument domain is the forward entry's: what it rejects is rejected here the same way, before any HIP call. */
+
+/* Gradients of aadff_render_psf_map_stack (S = 1: aadff_render_psf_map; S = 1, grid = 1: aadff_render_psf), i.e. the
+ * autograd of deeplens/render_psf.py:12-73 (reflect pad :57, flipped depthwise conv2d per patch :59-72), summed over the
+ * slice loop of 2_aber_aware_dff_aif.py:104-114.  img [B,C,H,W], psf_maps [S,C,g*ks,g*ks], dy [B,C,S,H,W] contiguous,
+ * d_img [B,C,H,W] (sum over the slices; PSF chosen by the patch of the dy pixel, halo folded back over the reflect
+ * padding), d_psf [S,C,g*ks,g*ks] (sum over the batch).  d_psf needs `workspace`: device memory of at least
+ * aadff_render_psf_map_stack_bwd_workspace bytes (partial sums per 32 x 32 tile, added in a fixed order by a second
+ * kernel); it may be NULL / 0 when d_psf is NULL. */
+int aadff_render_psf_map_stack_bwd(const float* img, const float* psf_maps, const float* dy,
+                                   float* d_img_or_null, float* d_psf_or_null, void* workspace, size_t workspace_bytes,
+                                   int B, int C, int S, int H, int W, int grid, int ks, aadff_stream_t stream);
+/* Workspace bytes of the call above for the same shape (host arithmetic only, no device needed; monotone in B and S). */
+int aadff_render_psf_map_stack_bwd_workspace(int B, int C, int S, int H, int W, int grid, int ks, size_t* bytes);
+
+/* Gradients of aadff_local_psf_render, i.e. the autograd of deeplens/render_psf.py:76-107 (replicate pad :93, unfold :99,
+ * product with the per-pixel kernels and sum :100-104, fold :105).  dy [B,C,H,W], d_img [B,C,H,W] (taps that clamp onto
+ * a border pixel all land on it), d_psf [B,H,W,ks,ks] (sum over the channels). */
+int aadff_local_psf_render_bwd(const float* img, const float* psf, const float* dy,
+                               float* d_img_or_null, float* d_psf_or_null,
+                               int B, int C, int H, int W, int ks, aadff_stream_t stream);
 
 /* Thin-lens baseline renderer with the PSF evaluated in the kernel.  Replaces ThinLens.coc + ThinLens.render (4-D
  * branch), deeplens/psfnet.py:503-512,549-570: per pixel the circle of confusion of `depth` for focus distance
