@@ -9,8 +9,14 @@ to the image AND the PSF from hand-written HIP kernels (csrc/conv_bwd.hip throug
 
 The forward is the existing kernel: under torch.no_grad(), or when no input requires grad, every function returns exactly
 what the forward-only function returns.  `grid` / `kernel_size` get no gradient, integer inputs are converted as in the
-forward, double backward is not supported (it raises).  Not covered: gradients through the ray tracer, the fused
-PSF-network renderers, thinlens_render and the M1-layered stack.
+forward, double backward is not supported (it raises).
+
+`psfnet_render` / `psfnet_render_stack` are PSFNet.render / PSFNet.render_stack (deeplens/psfnet.py:393-450, the path the
+reference's training scripts render their stacks with) differentiable to the image, the DEPTH map and the focus distances: the
+fused kernel's forward, and a fused backward that recomputes it and runs the transposed network on the matrix cores
+(csrc/psfnet_bwd.hip, torch.ops.aadff.psfnet_render_rgbd_diff) - nothing is stored between forward and backward.
+
+Not covered: gradients through the ray tracer, thinlens_render and the M1-layered stack.
 """
 import importlib
 
@@ -121,3 +127,80 @@ def local_psf_render_high_res(input, psf, patch_size=[320, 480], kernel_size=11)
             j0, j1 = pj * patch_size[1], min((pj + 1) * patch_size[1], W)
             out[:, :, i0:i1, j0:j1] = local_psf_render(input[:, :, i0:i1, j0:j1], psf[:, i0:i1, j0:j1, :, :], kernel_size=kernel_size)
     return out
+
+
+# ---------------------------------------------------------------- PSF-network renderers (deeplens/psfnet.py:393-450)
+_DIFF_MODES = ("fp32", "torch")
+
+
+def _psfnet_stack(lens, img, depth, foc_dists):
+    """img [N,C,H,W], depth [N,H,W], foc_dists [N,S] on any device -> [N,C,S,H,W] with gradients."""
+    from . import psfnet_pack
+    mode = lens.mlp_precision
+    if mode not in _DIFF_MODES:
+        raise ValueError(f"aadff.diffrender: mlp_precision={mode!r} has no differentiable renderer; supported modes are 'fp32' (fused HIP "
+                         "backward) and 'torch' (torch autograd over the network)")
+    dev = next(lens.psfnet.parameters()).device
+    N, C, H, W = img.shape
+    ks = lens.kernel_size
+    x, d = _abi.f32c(img, dev), _abi.f32c(depth, dev)
+    foc_z = lens.depth2z(foc_dists.to(device=dev, dtype=torch.float32).reshape(N, -1))          # torch autograd: the clamp's chain rule
+    if mode == "torch":
+        z = lens.depth2z(d)
+        gx, gy = lens._field_grid(H, W, dev)
+        gx, gy = gx.unsqueeze(0).expand(N, H, W), gy.unsqueeze(0).expand(N, H, W)
+        slices = []
+        for i in range(foc_z.shape[1]):
+            o = torch.stack((gx, gy, z, foc_z[:, i].reshape(N, 1, 1).expand(N, H, W)), -1).float()
+            psf = lens.psfnet(o)
+            slices.append(local_psf_render(x, psf.reshape(N, H, W, ks, ks), ks))
+        return torch.stack(slices, dim=2)
+    _abi.require_gpu()
+    if dev.type != "cuda" or not psfnet_pack.supported(lens.psfnet):
+        raise ValueError("aadff.diffrender: this PSF network is outside what the fused kernel supports (psfnet_pack.supported) or not on "
+                         "the GPU; supported modes are 'fp32' for such a network on the GPU and 'torch'")
+    packed = lens._fused(dev)
+    wt, wt_exp = psfnet_pack.transposed(packed, lens.psfnet)
+    xs, ys = lens._field_axes(H, W, dev)
+    inv_range = float(np.float32(1.0) / np.float32(lens.d_max - lens.d_min))      # as psfnet_pack.render_rgbd
+    out, flags = torch.ops.aadff.psfnet_render_rgbd_diff(x, d, xs, ys, foc_z, float(lens.d_min), inv_range, packed.wpack, packed.bias, wt,
+                                                         list(wt_exp), list(packed.ins), list(packed.outs), ks)
+    if int(flags.item()) & 16:
+        raise psfnet_pack.ActivationOverflow("aadff: a hidden activation of the PSF network exceeded 65504, the range of the fp16 hi/lo "
+                                             "operand split of the fused kernel; use mlp_precision='torch' for this network")
+    return out
+
+
+def _psfnet_wants_grad(lens, *ts):
+    return _wants_grad(*ts) or (lens.mlp_precision == "torch" and _wants_grad(*lens.psfnet.parameters()))
+
+
+def psfnet_render_stack(lens, img, depth, foc_dists):
+    """PSFNet.render_stack with gradients: img [N,C,H,W], depth [N,1,H,W] (mm, < 0), foc_dists [N,S] (mm, < 0) -> [N,C,S,H,W].
+
+    Gradients go to `img`, `depth` and `foc_dists` (through depth2z = torch.clamp: exactly 0 for a depth or a focus distance outside
+    [d_max, d_min]); only those that are required are computed.  `lens.mlp_precision`:
+      "fp32"  (default) the fused forward kernel (bit-equal to lens.render_stack) and the fused HIP backward.  The network WEIGHTS get
+              no gradient on this path.
+      "torch" lens.psfnet under torch autograd + `local_psf_render` of this module: keeps every activation, also gives parameter gradients.
+      "fp16" / "bf16" raise ValueError, as does a network the fused kernel does not support in "fp32" mode: no silent fallback.
+    Under torch.no_grad(), or when nothing requires grad, this IS lens.render_stack.  Double backward raises."""
+    if not _psfnet_wants_grad(lens, img, depth, foc_dists):
+        return lens.render_stack(img, depth, foc_dists)
+    N, C, H, W = img.shape
+    return _psfnet_stack(lens, img, depth.reshape(N, H, W), foc_dists.reshape(N, -1)).to(img.device)
+
+
+def psfnet_render(lens, img, depth, foc_dist):
+    """PSFNet.render with gradients (see psfnet_render_stack): img [N,C,H,W], depth [N,1,H,W], foc_dist [N] -> [N,C,H,W], or the 3-D
+    branch img [C,H,W], depth [H,W], scalar foc_dist (a float, or a 0-d tensor that may require grad) -> [C,H,W]."""
+    if not _psfnet_wants_grad(lens, img, depth, foc_dist):
+        return lens.render(img, depth, foc_dist)
+    if len(img.shape) == 3:
+        H, W = depth.shape
+        fd = torch.as_tensor(foc_dist, dtype=torch.float32).reshape(1, 1)
+        return _psfnet_stack(lens, img.unsqueeze(0), depth.reshape(1, H, W), fd)[0, :, 0].to(img.device)
+    if len(img.shape) != 4:
+        raise ValueError("img should be [C,H,W] or [N,C,H,W]")
+    N, C, H, W = img.shape
+    return _psfnet_stack(lens, img, depth.reshape(N, H, W), foc_dist.reshape(N, 1))[:, :, 0].to(img.device)

@@ -7,6 +7,7 @@ libaadff.so on the current HIP stream.  With them the path is visible to FakeTen
 functions, so a backward through them raises torch's "not differentiable" error.  The differentiable
 forms of the image-space operators are separate ops (`render_psf_map_stack_diff`, `local_psf_render_diff`, at the end of
 the image-space section; public functions in aadff/diffrender.py): same forward kernels, backward in csrc/conv_bwd.hip.
+`psfnet_render_rgbd_diff` is the fused RGB-D renderer with gradients to the image, the depth map and foc_z (csrc/psfnet_bwd.hip).
 
 The deeplens mirror (deeplens/render_psf.py, deeplens/psfnet.py) calls these ops; the multi-launch planners
 (aadff/focal_stack.py, aadff/training.py) keep calling the ABI directly because they pass raw offsets into pinned rings.
@@ -258,6 +259,92 @@ def psfnet_render_rgbd(img: torch.Tensor, depth: torch.Tensor, xs: torch.Tensor,
 def _(img, depth, xs, ys, foc_z, d_min, inv_range, wpack, bias, in_features, out_features, ks, flags, precision=0):
     N, Cn, H, W = img.shape
     return img.new_empty((N, Cn, foc_z.numel() // N, H, W), dtype=torch.float32)
+
+
+# ---------------------------------------------------------------- differentiable RGB-D render (csrc/psfnet_bwd.hip)
+def psfnet_bwd_workspace_bytes(N, S, Cn, H, W, ks, need_input, need_img):
+    """Bytes of device workspace aadff_psfnet_render_rgbd_bwd needs (host arithmetic, no GPU)."""
+    nbytes = C.c_size_t(0)
+    lib = _abi.load_library()
+    if lib.aadff_psfnet_render_rgbd_bwd_workspace(N, S, Cn, H, W, ks, int(need_input), int(need_img), C.byref(nbytes)) != 0:
+        raise RuntimeError("aadff_psfnet_render_rgbd_bwd_workspace failed: " + lib.aadff_last_error().decode(errors="replace"))
+    return nbytes.value
+
+
+@custom_op("aadff::psfnet_render_rgbd_bwd", mutates_args=(), device_types="cuda")
+def psfnet_render_rgbd_bwd(img: torch.Tensor, depth: torch.Tensor, xs: torch.Tensor, ys: torch.Tensor, foc_z: torch.Tensor, dy: torch.Tensor,
+                           d_min: float, inv_range: float, wpack: torch.Tensor, bias: torch.Tensor, wtpack: torch.Tensor, wt_exp: List[int],
+                           in_features: List[int], out_features: List[int], ks: int, need_img: bool, need_depth: bool,
+                           need_foc: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(d_img [N,C,H,W], d_depth [N,H,W], d_foc_z [N,S]) of psfnet_render_rgbd; a gradient that is not needed is not computed and comes
+    back empty.  Workspace: 4 bytes per (n, slice, pixel) for d_depth / d_foc_z, the PSFs of ONE slice for d_img."""
+    N, Cn, H, W = img.shape
+    S = foc_z.numel() // N
+    x, d, fz, g = img.contiguous().float(), depth.contiguous().float(), foc_z.contiguous().float(), dy.contiguous().float()
+    d_img = torch.empty_like(x) if need_img else x.new_empty((0,))
+    d_depth = torch.empty((N, H, W), dtype=torch.float32, device=x.device) if need_depth else x.new_empty((0,))
+    d_foc = torch.empty((N, S), dtype=torch.float32, device=x.device) if need_foc else x.new_empty((0,))
+    with torch.cuda.device(x.device):
+        nbytes = psfnet_bwd_workspace_bytes(N, S, Cn, H, W, ks, need_depth or need_foc, need_img)
+        ws = torch.empty((max(1, (nbytes + 3) // 4),), dtype=torch.float32, device=x.device)
+        _abi.call("aadff_psfnet_render_rgbd_bwd", _abi.ptr(d), _abi.ptr(xs.contiguous().float()), _abi.ptr(ys.contiguous().float()), _abi.ptr(fz),
+                  C.c_float(d_min), C.c_float(inv_range), N, S, _abi.ptr(wpack), _abi.ptr(bias), _abi.ptr(wtpack), _ints(wt_exp), len(in_features),
+                  _ints(in_features), _ints(out_features), _abi.ptr(x), _abi.ptr(g), Cn, H, W, ks, _abi.ptr(d_img) if need_img else None,
+                  _abi.ptr(d_depth) if need_depth else None, _abi.ptr(d_foc) if need_foc else None, _abi.ptr(ws), C.c_size_t(nbytes), _st(x))
+    return d_img, d_depth, d_foc
+
+
+@psfnet_render_rgbd_bwd.register_fake
+def _(img, depth, xs, ys, foc_z, dy, d_min, inv_range, wpack, bias, wtpack, wt_exp, in_features, out_features, ks, need_img, need_depth, need_foc):
+    N, Cn, H, W = img.shape
+    e = img.new_empty((0,), dtype=torch.float32)
+    return (torch.empty_like(img, dtype=torch.float32, memory_format=torch.contiguous_format) if need_img else e,
+            img.new_empty((N, H, W), dtype=torch.float32) if need_depth else e,
+            img.new_empty((N, foc_z.numel() // N), dtype=torch.float32) if need_foc else e)
+
+
+@custom_op("aadff::psfnet_render_rgbd_diff", mutates_args=(), device_types="cuda")
+def psfnet_render_rgbd_diff(img: torch.Tensor, depth: torch.Tensor, xs: torch.Tensor, ys: torch.Tensor, foc_z: torch.Tensor, d_min: float,
+                            inv_range: float, wpack: torch.Tensor, bias: torch.Tensor, wtpack: torch.Tensor, wt_exp: List[int],
+                            in_features: List[int], out_features: List[int], ks: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """psfnet_render_rgbd (fp32-equivalent mode) with an autograd formula for img [N,C,H,W], depth [N,H,W] and foc_z [N,S]; the forward
+    is the same ABI call.  The network weights (wpack, bias, wtpack) get no gradient.  Returns (out [N,C,S,H,W], flags int32[1]): an op
+    with an autograd formula cannot write into an argument, so the kernel's saturation flag (bit 4) comes back as a second result."""
+    N, Cn, H, W = img.shape
+    S = foc_z.numel() // N
+    x, d, fz = img.contiguous().float(), depth.contiguous().float(), foc_z.contiguous().float()
+    out = torch.empty((N, Cn, S, H, W), dtype=torch.float32, device=x.device)
+    flags = torch.zeros(1, dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        _abi.call("aadff_psfnet_render_rgbd", _abi.ptr(d), _abi.ptr(xs.contiguous().float()), _abi.ptr(ys.contiguous().float()), _abi.ptr(fz),
+                  C.c_float(d_min), C.c_float(inv_range), N, S, _abi.ptr(wpack), _abi.ptr(bias), len(in_features), _ints(in_features),
+                  _ints(out_features), _abi.ptr(x), _abi.ptr(out), Cn, H, W, ks, 0, _abi.ptr(flags), _st(x))
+    return out, flags
+
+
+@psfnet_render_rgbd_diff.register_fake
+def _(img, depth, xs, ys, foc_z, d_min, inv_range, wpack, bias, wtpack, wt_exp, in_features, out_features, ks):
+    N, Cn, H, W = img.shape
+    return img.new_empty((N, Cn, foc_z.numel() // N, H, W), dtype=torch.float32), img.new_empty((1,), dtype=torch.int32)
+
+
+def _rgbd_setup(ctx, inputs, output):
+    img, depth, xs, ys, foc_z, d_min, inv_range, wpack, bias, wtpack, wt_exp, in_features, out_features, ks = inputs
+    ctx.save_for_backward(img, depth, xs, ys, foc_z, wpack, bias, wtpack)
+    ctx.consts = (d_min, inv_range, list(wt_exp), list(in_features), list(out_features), ks)
+
+
+def _rgbd_backward(ctx, dy, _dflags):
+    img, depth, xs, ys, foc_z, wpack, bias, wtpack = ctx.saved_tensors
+    d_min, inv_range, wt_exp, ins, outs, ks = ctx.consts
+    need_img, need_depth, need_foc = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[4]
+    d_img, d_depth, d_foc = torch.ops.aadff.psfnet_render_rgbd_bwd(img, depth, xs, ys, foc_z, dy, d_min, inv_range, wpack, bias, wtpack, wt_exp, ins, outs,
+                                                                   ks, need_img, need_depth, need_foc)
+    return ((d_img.reshape(img.shape) if need_img else None), (d_depth.reshape(depth.shape) if need_depth else None), None, None,
+            (d_foc.reshape(foc_z.shape) if need_foc else None), None, None, None, None, None, None, None, None, None)
+
+
+psfnet_render_rgbd_diff.register_autograd(_rgbd_backward, setup_context=_rgbd_setup)
 
 
 # ---------------------------------------------------------------- ray trace -> PSFs (deeplens/optics.py:888-1026)

@@ -32,6 +32,48 @@ def supported(mlp):
             and all(l.in_features <= MAX_WIDTH and l.out_features <= MAX_WIDTH for l in lin) and lin[-1].out_features <= MAX_OUT)
 
 
+def _fragments(w):
+    """w [n, k] fp32 -> flat fp16 tensor [tile = n/16][step = k/32][plane hi|lo][lane = kg*16 + m][8]: lane (m, kg) of (tile, step)
+    holds w[16 tile + m][32 step + 8 kg + 0..7], zero-padded to 16 rows / 32 columns (the MFMA A-fragment order of the kernels)."""
+    n, k = w.shape
+    npad, kpad = (n + 15) // 16 * 16, (k + 31) // 32 * 32
+    wp = torch.zeros((npad, kpad), dtype=torch.float32, device=w.device)
+    wp[:n, :k] = w
+    hi = wp.half()
+    lo = (wp - hi.float()).half()
+    # [tile, m, step, kg, e] -> [tile, step, plane, lane = kg*16 + m, e]
+    f = torch.stack((hi, lo), 0).reshape(2, npad // 16, 16, kpad // 32, 4, 8).permute(1, 3, 0, 4, 2, 5)
+    return f.contiguous().reshape(-1)
+
+
+def pack_transposed(mlp, device):
+    """(wtpack, exps): the TRANSPOSED weights W_l^T [in, out] of every layer in the same fragment order, concatenated - the A operand
+    of the backward chain d_h_{l-1} = W_l^T d_a_l (csrc/psfnet_bwd.hip) - each layer multiplied by 2^exps[l] so that its largest
+    |weight| lies in [2^9, 2^10).  Unscaled, the lo half of a weight below ~0.06 is an fp16 subnormal (module docstring): an absolute
+    3e-8 that is harmless in one row but is the SAME for every row, so it survives a sum over the rows (the focus-distance gradient,
+    whose terms cancel to a small fraction of their size).  Scaled, lo stays normal down to |w| = max / 2^13; the kernel carries a
+    power-of-two scale per row anyway and undoes sum(exps) with it."""
+    frags, exps = [], []
+    for l in linears_of(mlp):
+        wt = l.weight.detach().to(device=device, dtype=torch.float32).t()
+        wmax = float(wt.abs().max()) if wt.numel() else 0.0
+        e = 9 - int(np.floor(np.log2(wmax))) if 0.0 < wmax < float("inf") else 0
+        e = max(-64, min(64, e))
+        frags.append(_fragments(wt * float(2.0 ** e)))
+        exps.append(e)
+    return torch.cat(frags).contiguous(), exps
+
+
+def transposed(packed, mlp):
+    """`pack_transposed` cached on the PackedMLP it belongs to: built on first use, dropped with the pack when a parameter changes
+    (PSFNet._fused rebuilds the pack on `key`).  Returns (wtpack, exps)."""
+    if packed.key != PackedMLP.key_of(mlp):
+        raise ValueError("aadff: the PackedMLP is stale (a parameter changed since it was built)")
+    if getattr(packed, "wtpack", None) is None:
+        packed.wtpack, packed.wt_exp = pack_transposed(mlp, packed.wpack.device)
+    return packed.wtpack, packed.wt_exp
+
+
 class PackedMLP:
     """Device buffers for aadff_psfnet_forward; rebuilt when a parameter changes (version counters)."""
 
@@ -45,21 +87,16 @@ class PackedMLP:
         planes, biases = [], []
         for l in lin:
             w = l.weight.detach().to(device=device, dtype=torch.float32)          # [out, in]
-            n, k = w.shape
-            npad, kpad = (n + 15) // 16 * 16, (k + 31) // 32 * 32
-            wp = torch.zeros((npad, kpad), dtype=torch.float32, device=device)
-            wp[:n, :k] = w
-            hi = wp.half()
-            lo = (wp - hi.float()).half()
-            # [tile, m, step, kg, e] -> [tile, step, plane, lane = kg*16 + m, e]
-            f = torch.stack((hi, lo), 0).reshape(2, npad // 16, 16, kpad // 32, 4, 8).permute(1, 3, 0, 4, 2, 5)
-            planes.append(f.contiguous().reshape(-1))
+            n = w.shape[0]
+            npad = (n + 15) // 16 * 16
+            planes.append(_fragments(w))
             b = torch.zeros(npad, dtype=torch.float32, device=device)
             if l.bias is not None:
                 b[:n] = l.bias.detach().to(device=device, dtype=torch.float32)
             biases.append(b)
         self.wpack = torch.cat(planes).contiguous()
         self.bias = torch.cat(biases).contiguous()
+        self.wtpack, self.wt_exp = None, None      # transposed pack for the backward, built on first use (transposed())
         self.flags = torch.zeros(1, dtype=torch.int32, device=device)
         wmax = max(float(l.weight.detach().abs().max()) for l in lin)
         if not wmax <= 65504.0:

@@ -475,6 +475,31 @@ int aadff_psfnet_render_rgbd(const float* depth, const float* xs, const float* y
                              const int* in_features, const int* out_features, const float* img, float* out, int C, int H,
                              int W, int ks, int precision, int* flags_or_null, aadff_stream_t stream);
 
+/* Gradients of aadff_psfnet_render_rgbd (precision 0) to the image, the depth map and foc_z (csrc/psfnet_bwd.hip), i.e. the
+ * autograd of PSFNet.render over the slice loop: deeplens/psfnet.py:393-450 (coordinate rows, depth2z = torch.clamp :447-450),
+ * deeplens/psfnet_arch.py:24-47 (Linear + ReLU ..., Linear + Sigmoid, F.normalize p=1) and deeplens/render_psf.py:76-107
+ * (per-pixel gather, replicate padding).  The network weights get no gradient.  Nothing is kept from the forward: the
+ * kernel recomputes it with the forward's arithmetic, keeps one ReLU mask bit per hidden unit on the CU and runs the
+ * transposed chain on the matrix cores with the forward's fp16 hi/lo operand split, every row scaled by a power of two.
+ *   dy [N,C,S,H,W] contiguous; wtpack: the TRANSPOSED weights in the fragment order of wpack, per layer
+ *   [in tile 16][k-step 32 over out_features][plane hi|lo][lane 64][8 halves] of W_l^T * 2^wt_exp[l], |wt_exp[l]| <= 64: a power
+ *   of two per layer that keeps the lo halves of small weights out of fp16's subnormal range; the kernel undoes the product of
+ *   the scales at the end (aadff/psfnet_pack.py: pack_transposed).  Both may be NULL when only d_img is asked for.
+ *   d_depth [N,H,W]: sum over the slices in slice order of d_z * inv_range where 0 <= (depth - d_min) * inv_range <= 1,
+ *     exactly 0 outside (the autograd of torch.clamp);  d_foc_z [N,S];  d_img [N,C,H,W]: sum over the slices in slice order.
+ * An output whose pointer is NULL is not computed (all NULL is an error).  workspace: device memory of at least
+ * aadff_psfnet_render_rgbd_bwd_workspace bytes: 4 bytes per row (n, s, y, x) and 4 per 64 rows when d_depth or d_foc_z is
+ * asked for (need_input), the network input and the PSFs of ONE slice (H*W*(4 + ks*ks) floats) when d_img is (need_img).
+ * Every sum has a fixed order (no float atomics): bitwise reproducible.  Arguments are checked before any HIP call. */
+int aadff_psfnet_render_rgbd_bwd(const float* depth, const float* xs, const float* ys, const float* foc_z, float d_min,
+                                 float inv_range, long N, int S, const void* wpack, const float* bias, const void* wtpack,
+                                 const int* wt_exp, int n_layers, const int* in_features, const int* out_features, const float* img,
+                                 const float* dy, int C, int H, int W, int ks, float* d_img_or_null, float* d_depth_or_null,
+                                 float* d_foc_z_or_null, void* workspace, size_t workspace_bytes, aadff_stream_t stream);
+/* Workspace bytes of the call above (host arithmetic only, no device needed). */
+int aadff_psfnet_render_rgbd_bwd_workspace(long N, int S, int C, int H, int W, int ks, int need_input, int need_img,
+                                           size_t* bytes);
+
 /* Refocus S lens states in one launch: trace spp rays from (0,0,depth[s]) (green table),
  * least-squares axis crossing -> d_sensor, then hfov/foclen/fnum.  Replaces
  * Lensgroup.refocus + post_computation + calc_fov + calc_efl,
