@@ -97,6 +97,9 @@ PROTOTYPES = {
     "aadff_render_psf_map_stack_bwd_workspace": [_I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_size_t)],
     "aadff_local_psf_render_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "aadff_thinlens_render": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _P],
+    "aadff_thinlens_render_stack": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _P],
+    "aadff_thinlens_render_stack_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _P],
+    "aadff_thinlens_render_stack_bwd_workspace": [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_size_t)],
     "aadff_trace_rays": [_P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P],
     "aadff_trace_rays_strict": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _F, _P, _P, _P],
     "aadff_trace_rays_strict_batched": [_P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],

@@ -16,7 +16,12 @@ reference's training scripts render their stacks with) differentiable to the ima
 fused kernel's forward, and a fused backward that recomputes it and runs the transposed network on the matrix cores
 (csrc/psfnet_bwd.hip, torch.ops.aadff.psfnet_render_rgbd_diff) - nothing is stored between forward and backward.
 
-Not covered: gradients through the ray tracer, thinlens_render and the M1-layered stack.
+`thinlens_render` / `thinlens_render_stack` are ThinLens.render (deeplens/psfnet.py:549-570, the baseline lens of
+dff.factory.get_lens) and its stack form with the same three gradients: the fused forward kernels, and a fused backward that
+re-evaluates every pixel's Gaussian PSF in the kernel (csrc/thinlens_bwd.hip, torch.ops.aadff.thinlens_render_stack_diff) - no
+[N,H,W,ks,ks] tensor in either direction.  With them both lens models of dff.factory.get_lens have a differentiable renderer.
+
+Not covered: gradients through the ray tracer and the M1-layered stack.
 """
 import importlib
 
@@ -204,3 +209,68 @@ def psfnet_render(lens, img, depth, foc_dist):
         raise ValueError("img should be [C,H,W] or [N,C,H,W]")
     N, C, H, W = img.shape
     return _psfnet_stack(lens, img, depth.reshape(N, H, W), foc_dist.reshape(N, 1))[:, :, 0].to(img.device)
+
+
+# ---------------------------------------------------------------- thin-lens baseline (deeplens/psfnet.py:489-570)
+_THIN_KS = (3, 5, 7, 9, 11, 13)
+
+
+def _thinlens_tensor_form(lens, img, depth, fd):
+    """The reference's tensor form (psfnet.py:549-570) under torch autograd: lens.coc -> [N,H,W,ks,ks] Gaussian PSFs -> `local_psf_render`
+    of this module.  The path of shapes outside the fused kernels' domain."""
+    ks, dev = lens.kernel_size, img.device
+    N, C, H, W = img.shape
+    fdm = fd.reshape(N, 1, 1, 1).expand(N, 1, H, W)
+    x, y = torch.meshgrid(torch.linspace(-ks / 2 + 1 / 2, ks / 2 - 1 / 2, ks), torch.linspace(ks / 2 - 1 / 2, -ks / 2 + 1 / 2, ks), indexing="xy")
+    x, y = x.to(dev), y.to(dev)
+    rad = lens.coc(depth, fdm).squeeze(1).unsqueeze(-1).unsqueeze(-1) / 2
+    psf = torch.exp(-(x ** 2 + y ** 2) / 2 / rad ** 2) / (2 * np.pi * rad ** 2)
+    psf = psf * (x ** 2 + y ** 2 < rad ** 2)
+    psf = psf / psf.sum((-1, -2)).unsqueeze(-1).unsqueeze(-1)
+    return local_psf_render(img, psf, ks)
+
+
+def _thinlens_stack(lens, img, depth, foc_dists):
+    """img [N,C,H,W], depth [N,1,H,W], foc_dists [N,S] on any device -> [N,C,S,H,W] on the GPU, with gradients."""
+    N, C, H, W = img.shape
+    S = foc_dists.shape[1]
+    if img.numel() == 0 or S == 0:
+        zero = img.to(torch.float32).sum() * 0 + depth.to(device=img.device, dtype=torch.float32).sum() * 0 \
+            + foc_dists.to(device=img.device, dtype=torch.float32).sum() * 0
+        return zero.expand((N, C, S, H, W)) * 1
+    dev = _dev(img)
+    x, d, f = _abi.f32c(img, dev), _abi.f32c(depth, dev), _abi.f32c(foc_dists, dev)
+    ks = lens.kernel_size
+    if C > 4 or ks not in _THIN_KS:
+        return torch.stack([_thinlens_tensor_form(lens, x, d, f[:, i]) for i in range(S)], dim=2)
+    return torch.ops.aadff.thinlens_render_stack_diff(x, d, f, ks, float(lens.foc_len), float(lens.fnum), float(lens.ps), float(lens.d_min),
+                                                      float(lens.d_max))
+
+
+def thinlens_render_stack(lens, img, depth, foc_dists):
+    """ThinLens.render_stack with gradients: img [N,C,H,W], depth [N,1,H,W] (mm, either sign convention), foc_dists [N,S] -> [N,C,S,H,W].
+
+    Gradients go to `img`, `depth` and `foc_dists`; only those that are required are computed.  They are the autograd of the reference's
+    tensor form with the disc mask as a constant: exactly 0 for a depth outside [d_min, d_max] and where the 0.1 px floor of the circle of
+    confusion is active, and bit-identical from run to run.  C <= 4 and kernel_size in {3, 5, ..., 13}: the fused HIP forward (bit-equal
+    to lens.render_stack) and the fused HIP backward; any other shape: the reference's tensor form under torch autograd with
+    `local_psf_render` of this module, one slice at a time.  Under torch.no_grad(), or when nothing requires grad, this IS
+    lens.render_stack.  Double backward raises."""
+    if len(img.shape) != 4:
+        raise ValueError("ThinLens.render_stack needs [N,C,H,W] (the reference's 3-D branch calls methods ThinLens lacks)")
+    N, C, H, W = img.shape
+    if not _wants_grad(img, depth, foc_dists):
+        return lens.render_stack(img, depth, foc_dists)
+    S = foc_dists.shape[-1] if foc_dists.dim() == 2 else foc_dists.numel() // max(N, 1)
+    return _thinlens_stack(lens, img, depth.reshape(N, 1, H, W), foc_dists.reshape(N, S)).to(img.device)
+
+
+def thinlens_render(lens, img, depth, foc_dist):
+    """ThinLens.render with gradients (see thinlens_render_stack): img [N,C,H,W], depth [N,1,H,W], foc_dist [N] -> [N,C,H,W].  The 3-D
+    branch raises the ValueError of ThinLens.render."""
+    if not _wants_grad(img, depth, foc_dist):
+        return lens.render(img, depth, foc_dist)
+    if len(img.shape) != 4:
+        raise ValueError("ThinLens.render needs [N,C,H,W] (the reference's 3-D branch calls methods ThinLens lacks)")
+    N, C, H, W = img.shape
+    return _thinlens_stack(lens, img, depth.reshape(N, 1, H, W), foc_dist.reshape(N, 1))[:, :, 0].to(img.device)

@@ -7,7 +7,9 @@ libaadff.so on the current HIP stream.  With them the path is visible to FakeTen
 functions, so a backward through them raises torch's "not differentiable" error.  The differentiable
 forms of the image-space operators are separate ops (`render_psf_map_stack_diff`, `local_psf_render_diff`, at the end of
 the image-space section; public functions in aadff/diffrender.py): same forward kernels, backward in csrc/conv_bwd.hip.
-`psfnet_render_rgbd_diff` is the fused RGB-D renderer with gradients to the image, the depth map and foc_z (csrc/psfnet_bwd.hip).
+`psfnet_render_rgbd_diff` is the fused RGB-D renderer with gradients to the image, the depth map and foc_z (csrc/psfnet_bwd.hip);
+`thinlens_render_stack_diff` is the thin-lens baseline with gradients to the image, the depth map and the focus distances
+(csrc/thinlens_bwd.hip).
 
 The deeplens mirror (deeplens/render_psf.py, deeplens/psfnet.py) calls these ops; the multi-launch planners
 (aadff/focal_stack.py, aadff/training.py) keep calling the ABI directly because they pass raw offsets into pinned rings.
@@ -345,6 +347,108 @@ def _rgbd_backward(ctx, dy, _dflags):
 
 
 psfnet_render_rgbd_diff.register_autograd(_rgbd_backward, setup_context=_rgbd_setup)
+
+
+# ---------------------------------------------------------------- differentiable thin-lens baseline (csrc/thinlens_bwd.hip)
+def _thin_args(foc_len, fnum, pixel_size, d_min, d_max):
+    return (C.c_float(foc_len / fnum), C.c_float(foc_len), C.c_float(1.0 / pixel_size), C.c_float(d_min), C.c_float(d_max))
+
+
+def _thin_stack_forward(img, depth, foc_dists, ks, foc_len, fnum, pixel_size, d_min, d_max):
+    N, Cn, H, W = img.shape
+    S = foc_dists.numel() // N
+    x, d, fd = img.contiguous().float(), depth.contiguous().float().reshape(N, 1, H, W), foc_dists.contiguous().float().reshape(N, S)
+    neg = (d < 0).any().to(torch.int32).reshape(1)              # the reference's whole-tensor sign test, kept on the device
+    out = torch.empty((N, Cn, S, H, W), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _abi.call("aadff_thinlens_render_stack", _abi.ptr(x), _abi.ptr(d), _abi.ptr(fd), _abi.ptr(neg), _abi.ptr(out), N, Cn, S, H, W, ks,
+                  *_thin_args(foc_len, fnum, pixel_size, d_min, d_max), _st(x))
+    return out
+
+
+@custom_op("aadff::thinlens_render_stack", mutates_args=(), device_types="cuda")
+def thinlens_render_stack(img: torch.Tensor, depth: torch.Tensor, foc_dists: torch.Tensor, ks: int, foc_len: float, fnum: float,
+                          pixel_size: float, d_min: float, d_max: float) -> torch.Tensor:
+    """thinlens_render for foc_dists [N,S] -> [N,C,S,H,W]; slice s is bit-equal to thinlens_render(..., foc_dists[:, s])."""
+    return _thin_stack_forward(img, depth, foc_dists, ks, foc_len, fnum, pixel_size, d_min, d_max)
+
+
+@thinlens_render_stack.register_fake
+def _(img, depth, foc_dists, ks, foc_len, fnum, pixel_size, d_min, d_max):
+    N, Cn, H, W = img.shape
+    return img.new_empty((N, Cn, foc_dists.numel() // N, H, W), dtype=torch.float32)
+
+
+def thinlens_bwd_workspace_bytes(N, Cn, S, H, W, ks, need_img, need_foc):
+    """Bytes of device workspace aadff_thinlens_render_stack_bwd needs (host arithmetic, no GPU):
+    4 * ((2 * N*S*H*W if need_img) + (N*S*H*ceil(W/64) if need_foc))."""
+    nbytes = C.c_size_t(0)
+    lib = _abi.load_library()
+    if lib.aadff_thinlens_render_stack_bwd_workspace(N, Cn, S, H, W, ks, int(need_img), int(need_foc), C.byref(nbytes)) != 0:
+        raise RuntimeError("aadff_thinlens_render_stack_bwd_workspace failed: " + lib.aadff_last_error().decode(errors="replace"))
+    return nbytes.value
+
+
+@custom_op("aadff::thinlens_render_stack_bwd", mutates_args=(), device_types="cuda")
+def thinlens_render_stack_bwd(img: torch.Tensor, depth: torch.Tensor, foc_dists: torch.Tensor, dy: torch.Tensor, ks: int, foc_len: float,
+                              fnum: float, pixel_size: float, d_min: float, d_max: float, need_img: bool, need_depth: bool,
+                              need_foc: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(d_img [N,C,H,W], d_depth [N,1,H,W], d_foc [N,S]) of thinlens_render_stack; a gradient that is not needed is not computed and
+    comes back empty.  Workspace: 8 bytes per (n, slice, pixel) for d_img, 4 bytes per 64-pixel run and slice for d_foc."""
+    N, Cn, H, W = img.shape
+    S = foc_dists.numel() // N
+    x, d, fd = img.contiguous().float(), depth.contiguous().float().reshape(N, 1, H, W), foc_dists.contiguous().float().reshape(N, S)
+    g = dy.contiguous().float()
+    neg = (d < 0).any().to(torch.int32).reshape(1)
+    d_img = torch.empty_like(x) if need_img else x.new_empty((0,))
+    d_depth = torch.empty_like(d) if need_depth else x.new_empty((0,))
+    d_foc = torch.empty_like(fd) if need_foc else x.new_empty((0,))
+    with torch.cuda.device(x.device):
+        nbytes = thinlens_bwd_workspace_bytes(N, Cn, S, H, W, ks, need_img, need_foc)
+        ws = torch.empty((max(1, (nbytes + 3) // 4),), dtype=torch.float32, device=x.device)
+        _abi.call("aadff_thinlens_render_stack_bwd", _abi.ptr(x), _abi.ptr(d), _abi.ptr(fd), _abi.ptr(neg), _abi.ptr(g),
+                  _abi.ptr(d_img) if need_img else None, _abi.ptr(d_depth) if need_depth else None, _abi.ptr(d_foc) if need_foc else None,
+                  _abi.ptr(ws), C.c_size_t(nbytes), N, Cn, S, H, W, ks, *_thin_args(foc_len, fnum, pixel_size, d_min, d_max), _st(x))
+    return d_img, d_depth, d_foc
+
+
+@thinlens_render_stack_bwd.register_fake
+def _(img, depth, foc_dists, dy, ks, foc_len, fnum, pixel_size, d_min, d_max, need_img, need_depth, need_foc):
+    N, Cn, H, W = img.shape
+    return (torch.empty_like(img, dtype=torch.float32, memory_format=torch.contiguous_format) if need_img else img.new_empty((0,), dtype=torch.float32),
+            img.new_empty((N, 1, H, W) if need_depth else (0,), dtype=torch.float32),
+            img.new_empty((N, foc_dists.numel() // N) if need_foc else (0,), dtype=torch.float32))
+
+
+@custom_op("aadff::thinlens_render_stack_diff", mutates_args=(), device_types="cuda")
+def thinlens_render_stack_diff(img: torch.Tensor, depth: torch.Tensor, foc_dists: torch.Tensor, ks: int, foc_len: float, fnum: float,
+                               pixel_size: float, d_min: float, d_max: float) -> torch.Tensor:
+    """thinlens_render_stack with an autograd formula for img [N,C,H,W], depth [N,1,H,W] and foc_dists [N,S]; the forward is the same
+    ABI call."""
+    return _thin_stack_forward(img, depth, foc_dists, ks, foc_len, fnum, pixel_size, d_min, d_max)
+
+
+@thinlens_render_stack_diff.register_fake
+def _(img, depth, foc_dists, ks, foc_len, fnum, pixel_size, d_min, d_max):
+    N, Cn, H, W = img.shape
+    return img.new_empty((N, Cn, foc_dists.numel() // N, H, W), dtype=torch.float32)
+
+
+def _thin_setup(ctx, inputs, output):
+    img, depth, foc_dists = inputs[:3]
+    ctx.save_for_backward(img, depth, foc_dists)
+    ctx.consts = tuple(inputs[3:])
+
+
+def _thin_backward(ctx, dy):
+    img, depth, foc_dists = ctx.saved_tensors
+    need_img, need_depth, need_foc = ctx.needs_input_grad[:3]
+    d_img, d_depth, d_foc = torch.ops.aadff.thinlens_render_stack_bwd(img, depth, foc_dists, dy, *ctx.consts, need_img, need_depth, need_foc)
+    return ((d_img.reshape(img.shape) if need_img else None), (d_depth.reshape(depth.shape) if need_depth else None),
+            (d_foc.reshape(foc_dists.shape) if need_foc else None), None, None, None, None, None, None)
+
+
+thinlens_render_stack_diff.register_autograd(_thin_backward, setup_context=_thin_setup)
 
 
 # ---------------------------------------------------------------- ray trace -> PSFs (deeplens/optics.py:888-1026)

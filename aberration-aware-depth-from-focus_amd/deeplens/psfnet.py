@@ -602,6 +602,28 @@ class ThinLens(DeepObj):
         return out.to(img.device)
 
     @torch.no_grad()
+    def render_stack(self, img, depth, foc_dists):
+        """[N,C,S,H,W] focal stack of img [N,C,H,W] for depth [N,1,H,W] and focus distances [N,S] (an extension, as
+        PSFNet.render_stack): bit-equal to `stack([render(img, depth, foc_dists[:, i]) for i], dim=2)`, as ONE launch
+        that stages every image window once (aadff_thinlens_render_stack) where the fused kernel applies, else that loop.
+        `aadff.diffrender.thinlens_render_stack` is this function with gradients."""
+        if len(img.shape) != 4:
+            raise ValueError("ThinLens.render_stack needs [N,C,H,W] (the reference's 3-D branch calls methods ThinLens lacks)")
+        N, C, H, W = img.shape
+        ks = self.kernel_size
+        S = foc_dists.shape[-1] if foc_dists.dim() == 2 else foc_dists.numel() // max(N, 1)
+        foc_dists = foc_dists.reshape(N, S)
+        if C > 4 or ks not in (3, 5, 7, 9, 11, 13) or S == 0 or img.numel() == 0:
+            sl = [self.render(img, depth, foc_dists[:, i]) for i in range(S)]
+            return torch.stack(sl, dim=2) if sl else torch.zeros((N, C, 0, H, W), dtype=torch.float32, device=img.device)
+        from aadff import _abi, ops  # noqa: F401
+        _abi.require_gpu()
+        dev = img.device if img.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        out = torch.ops.aadff.thinlens_render_stack(_abi.f32c(img, dev), _abi.f32c(depth, dev), _abi.f32c(foc_dists, dev), ks, float(self.foc_len),
+                                                    float(self.fnum), float(self.ps), float(self.d_min), float(self.d_max))
+        return out.to(img.device)
+
+    @torch.no_grad()
     def render_psf_tensor(self, img, depth, foc_dist):
         """The reference's literal form: build the [N,H,W,ks,ks] Gaussian PSFs with torch ops, then local_psf_render."""
         ks, dev = self.kernel_size, img.device

@@ -198,6 +198,34 @@ int aadff_thinlens_render(const float* img, const float* depth, const float* foc
                           float* out, int B, int C, int H, int W, int ks, float foc_len_over_fnum, float foc_len,
                           float inv_pixel_size, float d_min, float d_max, aadff_stream_t stream);
 
+/* ---- differentiable thin-lens baseline (csrc/thinlens_bwd.hip).  In the reference ThinLens.render is plain torch without
+ * @torch.no_grad(), differentiable in the image, the depth map and the focus distance; the entries below are its stack-fused
+ * forward and those gradients as closed forms.  Lens constants and `negate_or_null` as in aadff_thinlens_render;
+ * the argument domain is its domain (C <= 4, ks in {3,5,...,13}) with S >= 1, checked before any HIP call. */
+
+/* aadff_thinlens_render for S focus distances per batch item with the image window staged once: foc_dists [B,S],
+ * out [B,C,S,H,W]; slice s is bit-equal to aadff_thinlens_render with foc_dist = foc_dists[:, s]. */
+int aadff_thinlens_render_stack(const float* img, const float* depth, const float* foc_dists, const int* negate_or_null,
+                                float* out, int B, int C, int S, int H, int W, int ks, float foc_len_over_fnum, float foc_len,
+                                float inv_pixel_size, float d_min, float d_max, aadff_stream_t stream);
+
+/* Gradients of aadff_thinlens_render_stack: dy [B,C,S,H,W] -> d_img [B,C,H,W] (sum over the slices in slice order; taps that
+ * clamp onto a border pixel all land on it), d_depth [B,1,H,W] (sum over the slices in slice order; exactly 0 where the
+ * depth is outside [d_min, d_max] or the 0.1 px floor of the coc is active), d_foc [B,S].  The disc mask rho < r^2 is a
+ * constant, r^2 is computed exactly as the forward computes it.  A gradient whose pointer is NULL is not computed; all
+ * NULL is an error.  No float atomics: bitwise reproducible.  `workspace`: device memory of at least
+ * aadff_thinlens_render_stack_bwd_workspace bytes (r^2 and 1/Z per (b, slice, pixel) for d_img, one partial per
+ * workgroup for d_foc); may be NULL / 0 when only d_depth is wanted.  No [B,H,W,ks,ks] tensor is built. */
+int aadff_thinlens_render_stack_bwd(const float* img, const float* depth, const float* foc_dists, const int* negate_or_null,
+                                    const float* dy, float* d_img_or_null, float* d_depth_or_null, float* d_foc_or_null,
+                                    void* workspace, size_t workspace_bytes, int B, int C, int S, int H, int W, int ks,
+                                    float foc_len_over_fnum, float foc_len, float inv_pixel_size, float d_min, float d_max,
+                                    aadff_stream_t stream);
+/* Workspace bytes of the call above (host arithmetic only):
+ * 4 * ((need_img ? 2 * B*S*H*W : 0) + (need_foc ? B*S*H*ceil(W/64) : 0)). */
+int aadff_thinlens_render_stack_bwd_workspace(int B, int C, int S, int H, int W, int ks, int need_img, int need_foc,
+                                              size_t* bytes);
+
 /* ------------------------------------------------------------------ ray tracing */
 
 /* Generic trace of n rays through surfaces [first,last) in travel order (reverse when
