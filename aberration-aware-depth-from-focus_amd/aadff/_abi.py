@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("AADFF_LIB") or os.path.join(os.path.dirname(_HERE), "
 ABI_VERSION = 9
 MAX_GRID, MAX_KS, MAX_SURF, MAX_AI = 64, 51, 32, 8
 SURF_STOP, SURF_SPHERIC, SURF_ASPHERIC = 0, 1, 2
+DFOCUS_INTERP = {"none": 0, "parabola": 1, "gaussian": 2}        # AADFF_DFOCUS_*
 
 
 class Surface(C.Structure):
@@ -100,6 +101,7 @@ PROTOTYPES = {
     "aadff_thinlens_render_stack": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _P],
     "aadff_thinlens_render_stack_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _P],
     "aadff_thinlens_render_stack_bwd_workspace": [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_size_t)],
+    "aadff_depth_from_stack": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P],
     "aadff_trace_rays": [_P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P],
     "aadff_trace_rays_strict": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _F, _P, _P, _P],
     "aadff_trace_rays_strict_batched": [_P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],

@@ -9,7 +9,8 @@ forms of the image-space operators are separate ops (`render_psf_map_stack_diff`
 the image-space section; public functions in aadff/diffrender.py): same forward kernels, backward in csrc/conv_bwd.hip.
 `psfnet_render_rgbd_diff` is the fused RGB-D renderer with gradients to the image, the depth map and foc_z (csrc/psfnet_bwd.hip);
 `thinlens_render_stack_diff` is the thin-lens baseline with gradients to the image, the depth map and the focus distances
-(csrc/thinlens_bwd.hip).
+(csrc/thinlens_bwd.hip).  `depth_from_stack` goes the other way: focal stack -> depth map, the classical estimator (csrc/dfocus.hip;
+public function in aadff/dfocus.py).
 
 The deeplens mirror (deeplens/render_psf.py, deeplens/psfnet.py) calls these ops; the multi-launch planners
 (aadff/focal_stack.py, aadff/training.py) keep calling the ABI directly because they pass raw offsets into pinned rings.
@@ -449,6 +450,39 @@ def _thin_backward(ctx, dy):
 
 
 thinlens_render_stack_diff.register_autograd(_thin_backward, setup_context=_thin_setup)
+
+
+# ---------------------------------------------------------------- depth from a focal stack (csrc/dfocus.hip)
+@custom_op("aadff::depth_from_stack", mutates_args=(), device_types="cuda")
+def depth_from_stack(stack: torch.Tensor, coords: torch.Tensor, window: int, interp: str, eps: float, want_aif: bool,
+                     want_volume: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(depth [N,1,H,W], index [N,1,H,W] int32, peak [N,1,H,W], aif [N,C,H,W], volume [N,S,H,W]) of stack [N,C,S,H,W] over the slice
+    abscissae coords [N,S]: window-summed modified Laplacian, first argmax over the slices, three-point fit (`interp` none / parabola /
+    gaussian) in one launch.  An output that is not wanted is not written and comes back empty.  No autograd formula:
+    the argmax has no gradient."""
+    N, Cn, S, H, W = stack.shape
+    if interp not in _abi.DFOCUS_INTERP:
+        raise ValueError(f"depth_from_stack: interp {interp!r} is not one of {sorted(_abi.DFOCUS_INTERP)}")
+    x, u = stack.contiguous().float(), coords.contiguous().float().reshape(N, S)
+    depth = torch.empty((N, 1, H, W), dtype=torch.float32, device=x.device)
+    index = torch.empty((N, 1, H, W), dtype=torch.int32, device=x.device)
+    peak = torch.empty_like(depth)
+    aif = torch.empty((N, Cn, H, W), dtype=torch.float32, device=x.device) if want_aif else x.new_empty((0,))
+    volume = torch.empty((N, S, H, W), dtype=torch.float32, device=x.device) if want_volume else x.new_empty((0,))
+    with torch.cuda.device(x.device):
+        _abi.call("aadff_depth_from_stack", _abi.ptr(x), _abi.ptr(u), _abi.ptr(depth), _abi.ptr(index), _abi.ptr(peak),
+                  _abi.ptr(aif) if want_aif else None, _abi.ptr(volume) if want_volume else None, N, Cn, S, H, W, window,
+                  _abi.DFOCUS_INTERP[interp], C.c_float(eps), _st(x))
+    return depth, index, peak, aif, volume
+
+
+@depth_from_stack.register_fake
+def _(stack, coords, window, interp, eps, want_aif, want_volume):
+    N, Cn, S, H, W = stack.shape
+    return (stack.new_empty((N, 1, H, W), dtype=torch.float32), stack.new_empty((N, 1, H, W), dtype=torch.int32),
+            stack.new_empty((N, 1, H, W), dtype=torch.float32),
+            stack.new_empty((N, Cn, H, W) if want_aif else (0,), dtype=torch.float32),
+            stack.new_empty((N, S, H, W) if want_volume else (0,), dtype=torch.float32))
 
 
 # ---------------------------------------------------------------- ray trace -> PSFs (deeplens/optics.py:888-1026)

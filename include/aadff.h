@@ -226,6 +226,28 @@ int aadff_thinlens_render_stack_bwd(const float* img, const float* depth, const 
 int aadff_thinlens_render_stack_bwd_workspace(int B, int C, int S, int H, int W, int ks, int need_img, int need_foc,
                                               size_t* bytes);
 
+/* ---- depth from a focal stack (csrc/dfocus.hip): the classical estimator, the counterpart of the renderers.
+ * Not in the reference, which estimates depth with networks only (dff/AiFNet.py). */
+enum { AADFF_DFOCUS_NONE = 0, AADFF_DFOCUS_PARABOLA = 1, AADFF_DFOCUS_GAUSSIAN = 2 };
+
+/* Focus measure, argmax over the slices and three-point peak fit in one launch and one pass over the stack.
+ *   stack [N,C,S,H,W] (C in 1..4, the layout every stack renderer here writes), coords [N,S]: the abscissa of every slice,
+ *   strictly monotone per row in either direction (not checked: device data), spacing free.
+ *   gray g = ((c0 + c1) + c2 ...) * float32(1/C); modified Laplacian ML = |(2g - g_left) - g_right| + |(2g - g_up) - g_down| with
+ *   replicate padding (exactly rounded: bit-reproducible); F_s = sum of ML over window x window (replicate padding of the ML map,
+ *   non-negative terms, rows then columns); s* = the first slice with the largest F_s; f0 = F_s*, u0 = coords[s*].
+ *   Fit, only for 0 < s* < S-1 and interp != NONE: h- = u0 - u[s*-1], h+ = u[s*+1] - u0; PARABOLA a = f0 - F[s*-1], b = f0 - F[s*+1];
+ *   GAUSSIAN a = log1p((f0 - F[s*-1]) / (F[s*-1] + eps)), b likewise; x = (a h+^2 - b h-^2) / (2 (b h- + a h+)), 0 for a zero
+ *   denominator, clamped to the interval between -h- and h+; otherwise x = 0.
+ *   depth [N,1,H,W] = u0 + x, index [N,1,H,W] int32 = s*, peak [N,1,H,W] = f0, aif [N,C,H,W] = stack[n,:,s*,y,x] (a copy),
+ *   volume [N,S,H,W] = F.  aif and volume are written only when their pointers are non-NULL; the other outputs do not depend on
+ *   that.  window in {1,3,5,7,9}, interp one of AADFF_DFOCUS_*, eps > 0.  No atomics, no workspace: bitwise reproducible.
+ *   Inputs are expected to be finite; a constant image gives F = 0, index 0, depth = coords[:,0], peak 0.
+ * Arguments are checked before any HIP call; the message names the offending one. */
+int aadff_depth_from_stack(const float* stack, const float* coords, float* depth, int* index, float* peak, float* aif_or_null,
+                           float* volume_or_null, int N, int C, int S, int H, int W, int window, int interp, float eps,
+                           aadff_stream_t stream);
+
 /* ------------------------------------------------------------------ ray tracing */
 
 /* Generic trace of n rays through surfaces [first,last) in travel order (reverse when
