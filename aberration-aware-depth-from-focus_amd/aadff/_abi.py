@@ -102,6 +102,10 @@ PROTOTYPES = {
     "aadff_thinlens_render_stack_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _P],
     "aadff_thinlens_render_stack_bwd_workspace": [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_size_t)],
     "aadff_depth_from_stack": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P],
+    "aadff_attention_depth": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "aadff_attention_depth_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "aadff_dff_loss_sums": [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "aadff_dff_loss_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "aadff_trace_rays": [_P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P],
     "aadff_trace_rays_strict": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _F, _P, _P, _P],
     "aadff_trace_rays_strict_batched": [_P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],

@@ -5,7 +5,8 @@
 Per slice the modified Laplacian of the gray image summed over a window, the first argmax over the slices and a three-point peak fit
 on the slice abscissae - one fused HIP launch that reads the stack once (csrc/dfocus.hip, `torch.ops.aadff.depth_from_stack`).  It needs
 no network and no lens model, so it serves as a baseline and as the initialiser of an analysis-by-synthesis fit through
-aadff.diffrender (examples/depth_from_focus_classic.py).  No gradients: the argmax has none.  There is no CPU fallback: without the HIP
+aadff.diffrender (examples/depth_from_focus_classic.py).  No gradients: the argmax has none (aadff.focus_head is the soft, differentiable
+counterpart).  There is no CPU fallback: without the HIP
 library or a GPU it raises like the renderers.
 """
 from collections import namedtuple

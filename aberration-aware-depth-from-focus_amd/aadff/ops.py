@@ -10,7 +10,8 @@ the image-space section; public functions in aadff/diffrender.py): same forward 
 `psfnet_render_rgbd_diff` is the fused RGB-D renderer with gradients to the image, the depth map and foc_z (csrc/psfnet_bwd.hip);
 `thinlens_render_stack_diff` is the thin-lens baseline with gradients to the image, the depth map and the focus distances
 (csrc/thinlens_bwd.hip).  `depth_from_stack` goes the other way: focal stack -> depth map, the classical estimator (csrc/dfocus.hip;
-public function in aadff/dfocus.py).
+public function in aadff/dfocus.py).  `attention_depth` and `dff_loss_sums` are the differentiable way back: the attention head over a
+stack's scores and the sums of its loss, each with a backward op of its own (csrc/focus_head.hip; public functions in aadff/focus_head.py).
 
 The deeplens mirror (deeplens/render_psf.py, deeplens/psfnet.py) calls these ops; the multi-launch planners
 (aadff/focal_stack.py, aadff/training.py) keep calling the ABI directly because they pass raw offsets into pinned rings.
@@ -483,6 +484,155 @@ def _(stack, coords, window, interp, eps, want_aif, want_volume):
             stack.new_empty((N, 1, H, W), dtype=torch.float32),
             stack.new_empty((N, Cn, H, W) if want_aif else (0,), dtype=torch.float32),
             stack.new_empty((N, S, H, W) if want_volume else (0,), dtype=torch.float32))
+
+
+# ---------------------------------------------------------------- differentiable depth head and loss (csrc/focus_head.hip)
+def _head_dims(scores, stack, aif_channels):
+    N, K, S, H, W = scores.shape
+    return N, K, stack.shape[1], aif_channels, S, H, W
+
+
+def attention_bwd_workspace_bytes(N, S, H, W):
+    """Bytes of device workspace aadff_attention_depth_bwd needs for d_foc: one float per wave and slice (include/aadff.h)."""
+    return 4 * N * S * 4 * ((H * ((W + 3) // 4) + 255) // 256)
+
+
+@custom_op("aadff::attention_depth", mutates_args=(), device_types="cuda")
+def attention_depth(scores: torch.Tensor, stack: torch.Tensor, foc_dists: torch.Tensor, normalize_attention: bool,
+                    aif_channels: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(depth [N,1,H,W], aif [N,Ca,H,W]) of scores [N,K,S,H,W] (K 1 or 2), stack [N,Ct,S,H,W] and foc_dists [N,S]: softmax or
+    normalised-softplus attention over the slices, expectation of the focus distances and attention-weighted composite of the first
+    Ca = aif_channels channels of the stack, in one launch.  Autograd formula for scores, stack and foc_dists."""
+    N, K, Ct, Ca, S, H, W = _head_dims(scores, stack, aif_channels)
+    z, x, fd = scores.contiguous().float(), stack.contiguous().float(), foc_dists.contiguous().float().reshape(N, S)
+    depth = torch.empty((N, 1, H, W), dtype=torch.float32, device=z.device)
+    aif = torch.empty((N, Ca, H, W), dtype=torch.float32, device=z.device)
+    with torch.cuda.device(z.device):
+        _abi.call("aadff_attention_depth", _abi.ptr(z), _abi.ptr(x), _abi.ptr(fd), _abi.ptr(depth), _abi.ptr(aif), N, K, Ct, Ca, S, H, W,
+                  int(normalize_attention), _st(z))
+    return depth, aif
+
+
+@attention_depth.register_fake
+def _(scores, stack, foc_dists, normalize_attention, aif_channels):
+    N, K, S, H, W = scores.shape
+    return scores.new_empty((N, 1, H, W), dtype=torch.float32), scores.new_empty((N, aif_channels, H, W), dtype=torch.float32)
+
+
+@custom_op("aadff::attention_depth_bwd", mutates_args=(), device_types="cuda")
+def attention_depth_bwd(scores: torch.Tensor, stack: torch.Tensor, foc_dists: torch.Tensor, g_depth: torch.Tensor, g_aif: torch.Tensor,
+                        normalize_attention: bool, aif_channels: int, need_scores: bool, need_stack: bool,
+                        need_foc: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(d_scores [N,K,S,H,W], d_stack [N,Ct,S,H,W], d_foc [N,S]) of attention_depth; the attention is recomputed from the scores.  A
+    gradient that is not needed is not computed and comes back empty; the others do not depend on that."""
+    N, K, Ct, Ca, S, H, W = _head_dims(scores, stack, aif_channels)
+    z, x, fd = scores.contiguous().float(), stack.contiguous().float(), foc_dists.contiguous().float().reshape(N, S)
+    gd, ga = g_depth.contiguous().float(), g_aif.contiguous().float()
+    d_z = torch.empty_like(z) if need_scores else z.new_empty((0,))
+    d_x = torch.empty_like(x) if need_stack else z.new_empty((0,))
+    d_fd = torch.empty_like(fd) if need_foc else z.new_empty((0,))
+    nbytes = attention_bwd_workspace_bytes(N, S, H, W) if need_foc else 0
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=z.device) if need_foc else None
+    with torch.cuda.device(z.device):
+        _abi.call("aadff_attention_depth_bwd", _abi.ptr(z), _abi.ptr(x), _abi.ptr(fd), _abi.ptr(gd), _abi.ptr(ga),
+                  _abi.ptr(d_z) if need_scores else None, _abi.ptr(d_x) if need_stack else None, _abi.ptr(d_fd) if need_foc else None,
+                  _abi.ptr(ws), C.c_size_t(nbytes), N, K, Ct, Ca, S, H, W, int(normalize_attention), _st(z))
+    return d_z, d_x, d_fd
+
+
+@attention_depth_bwd.register_fake
+def _(scores, stack, foc_dists, g_depth, g_aif, normalize_attention, aif_channels, need_scores, need_stack, need_foc):
+    N, K, S, H, W = scores.shape
+    e = lambda: scores.new_empty((0,), dtype=torch.float32)      # noqa: E731  (one each: outputs must not alias)
+    return (torch.empty_like(scores, dtype=torch.float32, memory_format=torch.contiguous_format) if need_scores else e(),
+            torch.empty_like(stack, dtype=torch.float32, memory_format=torch.contiguous_format) if need_stack else e(),
+            scores.new_empty((N, S), dtype=torch.float32) if need_foc else e())
+
+
+def _head_setup(ctx, inputs, output):
+    scores, stack, foc_dists, normalize_attention, aif_channels = inputs
+    ctx.save_for_backward(scores, stack, foc_dists)
+    ctx.consts = (normalize_attention, aif_channels)
+
+
+def _head_backward(ctx, g_depth, g_aif):
+    scores, stack, foc_dists = ctx.saved_tensors
+    need = ctx.needs_input_grad[:3]
+    d_z, d_x, d_fd = torch.ops.aadff.attention_depth_bwd(scores, stack, foc_dists, g_depth, g_aif, *ctx.consts, *need)
+    return ((d_z.reshape(scores.shape) if need[0] else None), (d_x.reshape(stack.shape) if need[1] else None),
+            (d_fd.reshape(foc_dists.shape) if need[2] else None), None, None)
+
+
+attention_depth.register_autograd(_head_backward, setup_context=_head_setup)
+
+
+def _loss_dims(depth, aif, gt_depth, gt_aif):
+    hw = lambda t: (t.shape[-2], t.shape[-1]) if t.numel() else (0, 0)      # noqa: E731
+    Ca = aif.shape[1] if aif.numel() else (gt_aif.shape[1] if gt_aif.numel() else 0)
+    return (depth.shape[0], Ca, *hw(depth), *hw(aif), *hw(gt_depth), *hw(gt_aif))
+
+
+def _opt(t):
+    return _abi.ptr(t) if t.numel() else None
+
+
+@custom_op("aadff::dff_loss_sums", mutates_args=(), device_types="cuda")
+def dff_loss_sums(depth: torch.Tensor, aif: torch.Tensor, gt_depth: torch.Tensor, gt_aif: torch.Tensor, mask_range: torch.Tensor) -> torch.Tensor:
+    """The six float64 sums of the depth-from-focus loss over the common top-left window of depth [N,1,Hd,Wd], aif [N,Ca,Ha,Wa],
+    gt_depth [N,1,Hg,Wg] and gt_aif [N,Ca,Hi,Wi]: (sum_mask |e|, |mask|, sum_mask e^2, sum |aif - gt_aif|, sum wx r(d_gx), sum wy r(d_gy)).
+    An empty tensor stands for one that is absent (aif and gt_aif go together); mask_range: the two floats {lo, hi} of the range mask or
+    empty for gt_depth > 0.  Autograd formula for depth and aif (include/aadff.h)."""
+    d, a, gd, ga = (t.contiguous().float() for t in (depth, aif, gt_depth, gt_aif))
+    rng = mask_range.contiguous().float()
+    dims = _loss_dims(d, a, gd, ga)
+    sums = torch.empty((6,), dtype=torch.float64, device=d.device)
+    nbytes = 48 * ((dims[0] * dims[2] * dims[3] + 1023) // 1024)
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=d.device)
+    with torch.cuda.device(d.device):
+        _abi.call("aadff_dff_loss_sums", _abi.ptr(d), _opt(a), _opt(gd), _opt(ga), _opt(rng), _abi.ptr(sums), _abi.ptr(ws), C.c_size_t(nbytes), *dims, _st(d))
+    return sums
+
+
+@dff_loss_sums.register_fake
+def _(depth, aif, gt_depth, gt_aif, mask_range):
+    return depth.new_empty((6,), dtype=torch.float64)
+
+
+@custom_op("aadff::dff_loss_bwd", mutates_args=(), device_types="cuda")
+def dff_loss_bwd(depth: torch.Tensor, aif: torch.Tensor, gt_depth: torch.Tensor, gt_aif: torch.Tensor, mask_range: torch.Tensor,
+                 g_sums: torch.Tensor, need_depth: bool, need_aif: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(d_depth, d_aif) of dff_loss_sums for the cotangents g_sums [6] of its sums, in the shapes of depth and aif, zero outside the
+    window.  A gradient that is not needed is not computed and comes back empty."""
+    d, a, gd, ga = (t.contiguous().float() for t in (depth, aif, gt_depth, gt_aif))
+    rng, g = mask_range.contiguous().float(), g_sums.contiguous().double()
+    d_d = torch.empty_like(d) if need_depth else d.new_empty((0,))
+    d_a = torch.empty_like(a) if need_aif else d.new_empty((0,))
+    with torch.cuda.device(d.device):
+        _abi.call("aadff_dff_loss_bwd", _abi.ptr(d), _opt(a), _opt(gd), _opt(ga), _opt(rng), _abi.ptr(g), _abi.ptr(d_d) if need_depth else None,
+                  _abi.ptr(d_a) if need_aif else None, *_loss_dims(d, a, gd, ga), _st(d))
+    return d_d, d_a
+
+
+@dff_loss_bwd.register_fake
+def _(depth, aif, gt_depth, gt_aif, mask_range, g_sums, need_depth, need_aif):
+    return (torch.empty_like(depth, dtype=torch.float32, memory_format=torch.contiguous_format) if need_depth else depth.new_empty((0,), dtype=torch.float32),
+            torch.empty_like(aif, dtype=torch.float32, memory_format=torch.contiguous_format) if need_aif else depth.new_empty((0,), dtype=torch.float32))
+
+
+def _loss_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def _loss_backward(ctx, g_sums):
+    depth, aif, gt_depth, gt_aif, mask_range = ctx.saved_tensors
+    need_depth, need_aif = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and aif.numel() > 0
+    if not (need_depth or need_aif):
+        return None, None, None, None, None
+    d_d, d_a = torch.ops.aadff.dff_loss_bwd(depth, aif, gt_depth, gt_aif, mask_range, g_sums, need_depth, need_aif)
+    return ((d_d.reshape(depth.shape) if need_depth else None), (d_a.reshape(aif.shape) if need_aif else None), None, None, None)
+
+
+dff_loss_sums.register_autograd(_loss_backward, setup_context=_loss_setup)
 
 
 # ---------------------------------------------------------------- ray trace -> PSFs (deeplens/optics.py:888-1026)

@@ -248,6 +248,51 @@ int aadff_depth_from_stack(const float* stack, const float* coords, float* depth
                            float* volume_or_null, int N, int C, int S, int H, int W, int window, int interp, float eps,
                            aadff_stream_t stream);
 
+/* ---- differentiable depth head and its loss (csrc/focus_head.hip): stage 2 ("attention") of the reference's
+ * AiFDepthNet.fit and AiFDepthNet.compute_loss (dff/AiFNet.py:376-434, 450-584) as fused kernels.
+ *
+ * The head.  scores [N,K,S,H,W] (K in {1,2}), stack [N,Ct,S,H,W] (Ct in 1..4) of which the first Ca channels are read in place,
+ * foc_dists [N,S] (any values, any order).  zd = scores[:,0], za = scores[:,K-1].
+ *   normalize == 0: pd = softmax_S(zd), pa = softmax_S(za) (the maximum is subtracted before exp).
+ *   normalize != 0: pd = softplus(zd) / sum_S softplus(zd) with torch's softplus (beta 1, threshold 20); pa likewise of za for
+ *                   K == 2, but pa = softmax_S(za) for K == 1 (the reference's asymmetry).
+ *   depth [N,1,H,W] = sum_s pd_s foc_dists[n,s]; aif [N,Ca,H,W] = sum_s pa_s stack[n,c,s].
+ * One launch, offsets in 64 bits, 16-byte accesses when W % 4 == 0 and the pointers are 16-byte aligned. */
+int aadff_attention_depth(const float* scores, const float* stack, const float* foc_dists, float* depth, float* aif, int N, int K,
+                          int Ct, int Ca, int S, int H, int W, int normalize, aadff_stream_t stream);
+
+/* Gradients of the call above for the cotangents g_depth [N,1,H,W] and g_aif [N,Ca,H,W]: d_scores [N,K,S,H,W], d_stack
+ * [N,Ct,S,H,W] (exact zeros in the channels from Ca on), d_foc [N,S].  The attention is recomputed from the scores; nothing of
+ * the forward is needed.  A gradient whose pointer is NULL is not computed (all NULL is an error); the others do not depend on
+ * that.  d_foc is reduced in two stages of fixed order, no atomics: bitwise reproducible.  `workspace`: device memory of at
+ * least 4 * N * S * 4 * ceil(H * ceil(W / 4) / 256) bytes (one partial per wave and slice) when d_foc is asked for, else it may be
+ * NULL / 0. */
+int aadff_attention_depth_bwd(const float* scores, const float* stack, const float* foc_dists, const float* g_depth, const float* g_aif,
+                              float* d_scores_or_null, float* d_stack_or_null, float* d_foc_or_null, void* workspace,
+                              size_t workspace_bytes, int N, int K, int Ct, int Ca, int S, int H, int W, int normalize,
+                              aadff_stream_t stream);
+
+/* The six sums of the loss over the common top-left window h x w of the tensors that are given: depth [N,1,Hd,Wd] (always),
+ * gt_depth [N,1,Hg,Wg], and aif [N,Ca,Ha,Wa] with gt_aif [N,Ca,Hi,Wi] (Ca in 1..4); at least one of gt_depth and gt_aif.
+ *   mask = gt_depth > 0, or range[0] <= gt_depth <= range[1] when `range_or_null` (two floats on the device) is given.
+ *   sums[0] = sum_mask |depth - gt_depth|, sums[1] = |mask|, sums[2] = sum_mask (depth - gt_depth)^2      (0 without gt_depth)
+ *   sums[3] = sum |aif - gt_aif|                                                                           (0 without gt_aif)
+ *   sums[4] = sum wx r(depth[y+1,x] - depth[y,x]), sums[5] = sum wy r(depth[y,x+1] - depth[y,x]), r(t) = sqrt(t^2 + 1e-6),
+ *             w = exp(-mean_c (150 (gt_aif' - gt_aif))^2) over the same pixel pair                        (0 without gt_aif)
+ * Terms are formed in float32 and added in float64: per-workgroup partials, then one fixed-order final sum (no atomics).
+ * `workspace`: at least 48 * ceil(N * h * w / 1024) bytes of device memory. */
+int aadff_dff_loss_sums(const float* depth, const float* aif_or_null, const float* gt_depth_or_null, const float* gt_aif_or_null,
+                        const float* range_or_null, double* sums, void* workspace, size_t workspace_bytes, int N, int Ca, int Hd,
+                        int Wd, int Ha, int Wa, int Hg, int Wg, int Hi, int Wi, aadff_stream_t stream);
+
+/* Gradients of the sums above for their cotangents g_sums (six doubles on the device; those of sums[1] and sums[2] are not used:
+ * the count and the mean square carry no gradient): d_depth [N,1,Hd,Wd], d_aif [N,Ca,Ha,Wa], zero outside the window, sign(0) = 0.
+ * A cotangent multiplies only terms that exist, so an infinite or nan cotangent of an empty sum leaves zeros.  A gradient whose
+ * pointer is NULL is not computed (both NULL is an error). */
+int aadff_dff_loss_bwd(const float* depth, const float* aif_or_null, const float* gt_depth_or_null, const float* gt_aif_or_null,
+                       const float* range_or_null, const double* g_sums, float* d_depth_or_null, float* d_aif_or_null, int N, int Ca,
+                       int Hd, int Wd, int Ha, int Wa, int Hg, int Wg, int Hi, int Wi, aadff_stream_t stream);
+
 /* ------------------------------------------------------------------ ray tracing */
 
 /* Generic trace of n rays through surfaces [first,last) in travel order (reverse when
