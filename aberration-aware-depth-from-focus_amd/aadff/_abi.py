@@ -17,6 +17,8 @@ ABI_VERSION = 9
 MAX_GRID, MAX_KS, MAX_SURF, MAX_AI = 64, 51, 32, 8
 SURF_STOP, SURF_SPHERIC, SURF_ASPHERIC = 0, 1, 2
 DFOCUS_INTERP = {"none": 0, "parabola": 1, "gaussian": 2}        # AADFF_DFOCUS_*
+VALID_MODES = {"mask": 0, "finite": 1}                           # AADFF_VALID_*
+DEPTH_METRIC_COLS, SSIM_TILE_H, SSIM_TILE_W = 16, 32, 64         # AADFF_DEPTH_METRIC_COLS, AADFF_SSIM_TILE_*
 
 
 class Surface(C.Structure):
@@ -106,6 +108,9 @@ PROTOTYPES = {
     "aadff_attention_depth_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "aadff_dff_loss_sums": [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "aadff_dff_loss_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "aadff_depth_metric_sums": [_P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _P],
+    "aadff_image_metric_sums": [_P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _P],
+    "aadff_quantise_u8_host": [_P, _P, _L],
     "aadff_trace_rays": [_P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P],
     "aadff_trace_rays_strict": [_P, _P, _P, _I, _P, _I, _I, _I, _I, _F, _P, _P, _P],
     "aadff_trace_rays_strict_batched": [_P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],

@@ -12,6 +12,8 @@ the image-space section; public functions in aadff/diffrender.py): same forward 
 (csrc/thinlens_bwd.hip).  `depth_from_stack` goes the other way: focal stack -> depth map, the classical estimator (csrc/dfocus.hip;
 public function in aadff/dfocus.py).  `attention_depth` and `dff_loss_sums` are the differentiable way back: the attention head over a
 stack's scores and the sums of its loss, each with a backward op of its own (csrc/focus_head.hip; public functions in aadff/focus_head.py).
+`depth_metric_sums` and `image_metric_sums` score the result: the per-image sums behind the reference's depth metrics and PSNR / SSIM
+(csrc/metrics.hip; public functions in aadff/metrics.py); their outputs carry no graph.
 
 The deeplens mirror (deeplens/render_psf.py, deeplens/psfnet.py) calls these ops; the multi-launch planners
 (aadff/focal_stack.py, aadff/training.py) keep calling the ABI directly because they pass raw offsets into pinned rings.
@@ -633,6 +635,86 @@ def _loss_backward(ctx, g_sums):
 
 
 dff_loss_sums.register_autograd(_loss_backward, setup_context=_loss_setup)
+
+
+# ---------------------------------------------------------------- evaluation metrics (csrc/metrics.hip)
+def depth_metric_workspace_bytes(N, H, W):
+    """Bytes of device workspace aadff_depth_metric_sums needs: one row of 16 doubles per workgroup of 1024 pixels (include/aadff.h)."""
+    return 128 * N * (((H * W + 3) // 4 + 255) // 256)
+
+
+def image_metric_workspace_bytes(N, Cn, H, W, ssim):
+    """Bytes of device workspace aadff_image_metric_sums needs: an int64 and a double per workgroup - per channel and 32 x 64 tile of
+    windows with SSIM, per 1024 values without (include/aadff.h)."""
+    if ssim:
+        return 16 * N * Cn * ((H - 6 + _abi.SSIM_TILE_H - 1) // _abi.SSIM_TILE_H) * ((W - 6 + _abi.SSIM_TILE_W - 1) // _abi.SSIM_TILE_W)
+    return 16 * N * (((Cn * H * W + 3) // 4 + 255) // 256)
+
+
+@custom_op("aadff::depth_metric_sums", mutates_args=(), device_types="cuda")
+def depth_metric_sums(est: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, conf: torch.Tensor, valid_mode: str) -> torch.Tensor:
+    """sums [N,16] float64 of est, gt [N,1,H,W] in one pass: count, the error sums, the three threshold counts, the confidence-weighted
+    sums and the counts of "finite" mode, one row per image (column numbering: include/aadff.h).  mask [N,1,H,W] bool
+    and conf [N,1,H,W]: an empty tensor stands for one that is absent.  valid_mode "mask" or "finite".  No autograd formula: the output
+    carries no graph."""
+    if valid_mode not in _abi.VALID_MODES:
+        raise ValueError(f"depth_metric_sums: valid_mode {valid_mode!r} is not one of {sorted(_abi.VALID_MODES)}")
+    e, g = est.detach().contiguous().float(), gt.detach().contiguous().float()
+    N, H, W = e.shape[0], e.shape[-2], e.shape[-1]
+    m = mask.contiguous() if mask.numel() else None
+    if m is not None and m.dtype != torch.bool:
+        m = m != 0
+    c = conf.detach().contiguous().float() if conf.numel() else None
+    sums = torch.empty((N, _abi.DEPTH_METRIC_COLS), dtype=torch.float64, device=e.device)
+    nbytes = depth_metric_workspace_bytes(N, H, W)
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=e.device)
+    with torch.cuda.device(e.device):
+        _abi.call("aadff_depth_metric_sums", _abi.ptr(e), _abi.ptr(g), _abi.ptr(m), _abi.ptr(c), _abi.ptr(sums), _abi.ptr(ws), C.c_size_t(nbytes),
+                  N, H, W, _abi.VALID_MODES[valid_mode], _st(e))
+    return sums
+
+
+@depth_metric_sums.register_fake
+def _(est, gt, mask, conf, valid_mode):
+    return est.new_empty((est.shape[0], _abi.DEPTH_METRIC_COLS), dtype=torch.float64)
+
+
+@custom_op("aadff::image_metric_sums", mutates_args=(), device_types="cuda")
+def image_metric_sums(pred: torch.Tensor, target: torch.Tensor, ssim: bool) -> torch.Tensor:
+    """sums [N,2] float64 of pred, target [N,C,H,W] (C in 1..4) quantised to bytes as the reference's batch_PSNR does: the exact sum of
+    squared differences and, with `ssim`, the sum of the SSIM index over all full 7 x 7 windows and channels (else 0).  No autograd
+    formula: the output carries no graph."""
+    x, y = pred.detach().contiguous().float(), target.detach().contiguous().float()
+    N, Cn, H, W = x.shape
+    sums = torch.empty((N, 2), dtype=torch.float64, device=x.device)
+    nbytes = image_metric_workspace_bytes(N, Cn, H, W, ssim) if (not ssim or (H >= 7 and W >= 7)) else 16
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _abi.call("aadff_image_metric_sums", _abi.ptr(x), _abi.ptr(y), _abi.ptr(sums), _abi.ptr(ws), C.c_size_t(nbytes), N, Cn, H, W, int(ssim),
+                  _st(x))
+    return sums
+
+
+@image_metric_sums.register_fake
+def _(pred, target, ssim):
+    return pred.new_empty((pred.shape[0], 2), dtype=torch.float64)
+
+
+# scores, not losses: an input that requires a gradient is accepted and the sums carry no graph
+def _metric_setup(ctx, inputs, output):
+    ctx.mark_non_differentiable(output)
+
+
+def _depth_metric_backward(ctx, g):
+    return None, None, None, None, None
+
+
+def _image_metric_backward(ctx, g):
+    return None, None, None
+
+
+depth_metric_sums.register_autograd(_depth_metric_backward, setup_context=_metric_setup)
+image_metric_sums.register_autograd(_image_metric_backward, setup_context=_metric_setup)
 
 
 # ---------------------------------------------------------------- ray trace -> PSFs (deeplens/optics.py:888-1026)

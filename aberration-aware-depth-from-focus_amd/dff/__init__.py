@@ -3,12 +3,15 @@
 `from dff import *` is how 2_aber_aware_dff_aif.py:25 / 2_aber_aware_dff_dfv.py:25 obtain `get_lens`, `get_dataset`,
 `select_focus_dist`, the dataset classes, `AiFDepthNet` and the `mask_*` metrics.  This package provides what belongs to the
 rendering path (`dataset`, `factory`, `utils`).  The depth-from-focus network (`dff/AiFNet.py`) and the evaluation
-metrics (`dff/metrics.py`) are consumers of rendered stacks, outside this package's scope:
+metrics (`dff/metrics.py`) are consumers of rendered stacks:
 
 * with `AADFF_REFERENCE_ROOT=/path/to/reference/checkout` (set by `python -m aadff.run_script`) those two modules are loaded
   from that checkout, file by file, as `dff.AiFNet` / `dff.metrics` and their public names are re-exported, so the
-  reference's scripts find every name they use;
-* without it each of their names is bound to a stub that raises an ImportError saying exactly that when it is called.
+  reference's scripts find every name they use (its `dff/metrics.py` needs scikit-image to load);
+* with `AADFF_NATIVE_METRICS=1` the metrics come from this package instead: `dff.metrics` is `aadff.metrics` (fused HIP kernels, no
+  scikit-image) and its names are bound here - every function of the reference's file except `get_bumpiness` and
+  `get_bumpiness_non_mask`, which `aadff.metrics` does not have and which stay stubs;
+* without either each of their names is bound to a stub that raises an ImportError saying exactly that when it is called.
 """
 import importlib.util as _ilu
 import os as _os
@@ -51,8 +54,16 @@ class _OutOfScope:
 
 def _load_consumers():
     root = _os.environ.get("AADFF_REFERENCE_ROOT", "")
+    native = _os.environ.get("AADFF_NATIVE_METRICS", "") == "1"
     for mod, names in _CONSUMER_NAMES.items():
         path, loaded, why = _os.path.join(root, "dff", mod + ".py"), None, None
+        if mod == "metrics" and native:                           # opt-in: this package's own metrics in place of the reference's file
+            import aadff.metrics as _native
+            _sys.modules["dff.metrics"] = globals()["metrics"] = _native
+            for k in names:
+                globals()[k] = getattr(_native, k) if hasattr(_native, k) else _OutOfScope(
+                    k, mod, "aadff.metrics has no bumpiness score: its Scharr filters differ between scikit-image versions (DESIGN.md 8).")
+            continue
         if root and _os.path.isfile(path):
             spec = _ilu.spec_from_file_location(f"dff.{mod}", path)
             loaded = _ilu.module_from_spec(spec)

@@ -293,6 +293,52 @@ int aadff_dff_loss_bwd(const float* depth, const float* aif_or_null, const float
                        const float* range_or_null, const double* g_sums, float* d_depth_or_null, float* d_aif_or_null, int N, int Ca,
                        int Hd, int Wd, int Ha, int Wa, int Hg, int Wg, int Hi, int Wi, aadff_stream_t stream);
 
+/* ---- evaluation metrics (csrc/metrics.hip): the depth scores of the reference's dff/metrics.py and the PSNR / SSIM of
+ * its batch_PSNR / batch_SSIM as per-image float64 sums that stay on the device.  No atomics: two fixed-order stages through the
+ * caller's workspace, bitwise reproducible. */
+enum { AADFF_VALID_MASK = 0, AADFF_VALID_FINITE = 1 };
+#define AADFF_DEPTH_METRIC_COLS 16
+#define AADFF_SSIM_TILE_H 32   /* 7 x 7 windows per workgroup of aadff_image_metric_sums: rows ... */
+#define AADFF_SSIM_TILE_W 64   /* ... and columns */
+
+/* One pass over est, gt [N,1,H,W] float32, mask_or_null [N,1,H,W] bytes (torch.bool's storage; non-zero = valid) and conf_or_null
+ * [N,1,H,W] float32 -> sums [N,16] float64, one row per image.  Per pixel, in float64 from the exactly converted float32 values e, g, c
+ * (IEEE division, the device's float64 log): d = g - e, rel = |d| / g, sq = d^2 / g, l2 = (log g - log e)^2, q = max(e / g, g / e) with
+ * a nan handed on as numpy.maximum does.  Columns:
+ *    0 count   1 sum |d|   2 sum d^2   3 sum rel   4 sum sq   5 sum l2   6, 7, 8 count of q < 1.25, 1.5625, 1.953125
+ *    9 sum c   10 sum c |d|   11 sum c d^2 (zero without conf)   12..15 the counts of FINITE mode, zero in MASK mode
+ * AADFF_VALID_MASK: over the pixels with mask != 0 (all pixels when the mask is NULL): the reference's mask_*, AIF_DepthNEt_*, mae, mse,
+ *   rmse and *_w_conf* functions are quotients of these columns.
+ * AADFF_VALID_FINITE (mask must be NULL): every pixel takes part, as in the reference's unmasked abs_rel, sq_rel, rmse_log and
+ *   accuracy_k (dff/metrics.py:10-43): an infinite rel, sq or l2 is left out of its sum, a nan is kept; column 12 counts the pixels
+ *   whose rel is not infinite, 13 those whose sq is not infinite, 14 those where neither log g nor log e is infinite (rmse_log divides
+ *   by that, not by the number of terms it kept), 15 those whose q is not infinite.  Columns 0-2 and 6-11 run over all pixels.
+ * An empty valid set leaves a row of zeros.  `workspace`: device memory of at least 128 * N * ceil(ceil(H * W / 4) / 256) bytes.
+ * 16-byte accesses when H * W % 4 == 0 (so with W % 4 == 0) and est, gt, conf are 16-byte and mask 4-byte aligned.
+ * Arguments are checked before any HIP call; the message names the offending one. */
+int aadff_depth_metric_sums(const float* est, const float* gt, const unsigned char* mask_or_null, const float* conf_or_null,
+                            double* sums, void* workspace, size_t workspace_bytes, int N, int H, int W, int valid_mode,
+                            aadff_stream_t stream);
+
+/* pred, target [N,C,H,W] float32, C in 1..4 -> sums [N,2] float64.  x, y = the images quantised as torch's
+ * img.mul(255).add_(0.5).clamp_(0, 255).to(uint8) does, every step rounded separately in float32 (a nan gives 0).
+ *   sums[n][0] = sum over channels and pixels of (x - y)^2, accumulated in 64-bit integers: exact.
+ *   sums[n][1] = sum over channels and over the (H-6)(W-6) full 7 x 7 windows of
+ *                S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)),  C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2,
+ *                u = window mean, v = sample (co)variance (n - 1 = 48): scikit-image's structural_similarity with its defaults on uint8
+ *                images, whose mean over the image cropped by 3 is this sum / ((H-6)(W-6)).  The five window sums are exact
+ *                integers; the (co)variance numerators 49 Sxx - Sx^2, 49 Syy - Sy^2, 49 Sxy - Sx Sy are formed in 64-bit integers and
+ *                only the last step is float64.  Computed only when want_ssim != 0 (else 0); H >= 7 and W >= 7 are then required.
+ * `workspace`: 8-byte aligned device memory of at least 16 * N * B bytes, B = C * ceil((H-6) / 32) * ceil((W-6) / 64) with want_ssim,
+ * else ceil(ceil(C * H * W / 4) / 256).  16-byte accesses when W % 4 == 0 (without want_ssim: C * H * W % 4 == 0) and both pointers
+ * are 16-byte aligned. */
+int aadff_image_metric_sums(const float* pred, const float* target, double* sums, void* workspace, size_t workspace_bytes, int N,
+                            int C, int H, int W, int want_ssim, aadff_stream_t stream);
+
+/* The quantisation rule of the kernel above, the same function compiled for the host: out[i] = byte of values[i], n >= 0 values in
+ * host memory.  For tests of the rule against torch; needs no GPU. */
+int aadff_quantise_u8_host(const float* values, unsigned char* out, long n);
+
 /* ------------------------------------------------------------------ ray tracing */
 
 /* Generic trace of n rays through surfaces [first,last) in travel order (reverse when
