@@ -108,6 +108,8 @@ PROTOTYPES = {
     "aadff_attention_depth_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "aadff_dff_loss_sums": [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "aadff_dff_loss_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "aadff_dfv_head_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "aadff_dfv_head_bwd": [_P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _P],
     "aadff_depth_metric_sums": [_P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _P],
     "aadff_image_metric_sums": [_P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _P],
     "aadff_quantise_u8_host": [_P, _P, _L],

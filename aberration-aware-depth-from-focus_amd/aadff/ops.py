@@ -12,6 +12,8 @@ the image-space section; public functions in aadff/diffrender.py): same forward 
 (csrc/thinlens_bwd.hip).  `depth_from_stack` goes the other way: focal stack -> depth map, the classical estimator (csrc/dfocus.hip;
 public function in aadff/dfocus.py).  `attention_depth` and `dff_loss_sums` are the differentiable way back: the attention head over a
 stack's scores and the sums of its loss, each with a backward op of its own (csrc/focus_head.hip; public functions in aadff/focus_head.py).
+`dfv_regress` is the head of the reference's second network: a low-resolution cost volume upsampled, softmaxed and regressed to depth and
+its standard deviation in one kernel, with a gather-form backward (csrc/dfv_head.hip; public functions in aadff/dfv_head.py).
 `depth_metric_sums` and `image_metric_sums` score the result: the per-image sums behind the reference's depth metrics and PSNR / SSIM
 (csrc/metrics.hip; public functions in aadff/metrics.py); their outputs carry no graph.
 
@@ -635,6 +637,88 @@ def _loss_backward(ctx, g_sums):
 
 
 dff_loss_sums.register_autograd(_loss_backward, setup_context=_loss_setup)
+
+
+# ---------------------------------------------------------------- cost-volume depth head (csrc/dfv_head.hip)
+def dfv_bwd_tiling(w, W):
+    """(TC, R): the cells of a cost row and the output rows one workgroup of the backward's first stage owns (include/aadff.h)."""
+    ratio = -(-W // w)
+    tc = min(max(240 // ratio - 1, 1), 8)
+    return tc, min(max(256 // ((tc + 1) * ratio + 1), 1), 8)
+
+
+def dfv_bwd_workspace_bytes(B, S, h, w, H, W, need_cost=True, need_foc=True):
+    """Bytes of device workspace aadff_dfv_head_bwd needs: the row sums [B,S,H,w] for d_cost and one partial per slice and workgroup
+    for d_foc (include/aadff.h)."""
+    tc, r = dfv_bwd_tiling(w, W)
+    return 4 * B * S * ((H * w if need_cost else 0) + (-(-H // r) * -(-w // tc) if need_foc else 0))
+
+
+@custom_op("aadff::dfv_regress", mutates_args=(), device_types="cuda")
+def dfv_regress(cost: torch.Tensor, foc_dists: torch.Tensor, height: int, width: int,
+                want_prob: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(pred [B,1,H,W], std [B,1,H,W], prob [B,S,H,W] or empty) of cost [B,S,h,w] and foc_dists [B,S]: bilinear upsampling to
+    height x width (ATen's align_corners = False), softmax over the slices, expectation of the focus distances and its standard
+    deviation in one launch.  Autograd formula for cost and foc_dists through pred; std and prob carry no graph."""
+    B, S, h, w = cost.shape
+    c, fd = cost.contiguous().float(), foc_dists.contiguous().float().reshape(B, S)
+    pred = torch.empty((B, 1, height, width), dtype=torch.float32, device=c.device)
+    std = torch.empty_like(pred)
+    prob = torch.empty((B, S, height, width) if want_prob else (0,), dtype=torch.float32, device=c.device)
+    with torch.cuda.device(c.device):
+        _abi.call("aadff_dfv_head_fwd", _abi.ptr(c), _abi.ptr(fd), _abi.ptr(pred), _abi.ptr(std), _abi.ptr(prob) if want_prob else None,
+                  B, S, h, w, height, width, _st(c))
+    return pred, std, prob
+
+
+@dfv_regress.register_fake
+def _(cost, foc_dists, height, width, want_prob):
+    B, S = cost.shape[0], cost.shape[1]
+    return (cost.new_empty((B, 1, height, width), dtype=torch.float32), cost.new_empty((B, 1, height, width), dtype=torch.float32),
+            cost.new_empty((B, S, height, width) if want_prob else (0,), dtype=torch.float32))
+
+
+@custom_op("aadff::dfv_regress_bwd", mutates_args=(), device_types="cuda")
+def dfv_regress_bwd(cost: torch.Tensor, foc_dists: torch.Tensor, g_pred: torch.Tensor, need_cost: bool,
+                    need_foc: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(d_cost [B,S,h,w], d_foc [B,S]) of dfv_regress for the cotangent g_pred [B,1,H,W]; the softmax is recomputed from the cost.  A
+    gradient that is not needed is not computed and comes back empty; the other does not depend on that."""
+    B, S, h, w = cost.shape
+    H, W = g_pred.shape[-2], g_pred.shape[-1]
+    c, fd, g = cost.contiguous().float(), foc_dists.contiguous().float().reshape(B, S), g_pred.contiguous().float()
+    d_c = torch.empty_like(c) if need_cost else c.new_empty((0,))
+    d_fd = torch.empty_like(fd) if need_foc else c.new_empty((0,))
+    nbytes = dfv_bwd_workspace_bytes(B, S, h, w, H, W, need_cost, need_foc)
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=c.device)
+    with torch.cuda.device(c.device):
+        _abi.call("aadff_dfv_head_bwd", _abi.ptr(c), _abi.ptr(fd), _abi.ptr(g), _abi.ptr(d_c) if need_cost else None,
+                  _abi.ptr(d_fd) if need_foc else None, _abi.ptr(ws), C.c_size_t(nbytes), B, S, h, w, H, W, _st(c))
+    return d_c, d_fd
+
+
+@dfv_regress_bwd.register_fake
+def _(cost, foc_dists, g_pred, need_cost, need_foc):
+    e = lambda: cost.new_empty((0,), dtype=torch.float32)      # noqa: E731  (one each: outputs must not alias)
+    return (torch.empty_like(cost, dtype=torch.float32, memory_format=torch.contiguous_format) if need_cost else e(),
+            cost.new_empty((cost.shape[0], cost.shape[1]), dtype=torch.float32) if need_foc else e())
+
+
+def _dfv_setup(ctx, inputs, output):
+    cost, foc_dists = inputs[:2]
+    ctx.save_for_backward(cost, foc_dists)
+    ctx.mark_non_differentiable(output[1], output[2])          # std is computed under no_grad in the reference; prob is its eval output
+
+
+def _dfv_backward(ctx, g_pred, g_std, g_prob):
+    cost, foc_dists = ctx.saved_tensors
+    need = ctx.needs_input_grad[:2]
+    if not any(need):
+        return None, None, None, None, None
+    d_c, d_fd = torch.ops.aadff.dfv_regress_bwd(cost, foc_dists, g_pred, *need)
+    return ((d_c.reshape(cost.shape) if need[0] else None), (d_fd.reshape(foc_dists.shape) if need[1] else None), None, None, None)
+
+
+dfv_regress.register_autograd(_dfv_backward, setup_context=_dfv_setup)
 
 
 # ---------------------------------------------------------------- evaluation metrics (csrc/metrics.hip)

@@ -293,6 +293,34 @@ int aadff_dff_loss_bwd(const float* depth, const float* aif_or_null, const float
                        const float* range_or_null, const double* g_sums, float* d_depth_or_null, float* d_aif_or_null, int N, int Ca,
                        int Hd, int Wd, int Ha, int Wa, int Hg, int Wg, int Hi, int Wi, aadff_stream_t stream);
 
+/* ---- cost-volume depth head (csrc/dfv_head.hip): what the reference's DFVNet puts between a decoder level's cost
+ * volume and its loss (DFV_models/DFFNet.py:94-95, 102-115; disparityregression of DFV_models/submodule.py:63-77) as fused kernels.
+ *
+ * cost [B,S,h,w], foc_dists [B,S] (any values, any order) -> for every pixel of the H x W output (H >= h, W >= w, any ratio):
+ *   z_s  = the bilinear interpolation of cost[b,s] with ATen's rule for align_corners = False, in float32: scale = float(in) / out,
+ *          src = max(scale * (dst + 0.5) - 0.5, 0), i0 = int(src), i1 = min(i0 + 1, in - 1), lambda = src - i0,
+ *          z = (1 - ly) ((1 - lx) c[y0,x0] + lx c[y0,x1]) + ly ((1 - lx) c[y1,x0] + lx c[y1,x1]);
+ *   p    = softmax_S(z) (the maximum is subtracted before exp: finite for costs of any size);
+ *   pred [B,1,H,W] = sum_s p_s foc_dists[b,s];   std [B,1,H,W] = sqrt(sum_s p_s (pred - foc_dists[b,s])^2);
+ *   prob [B,S,H,W] = p, written only when the pointer is non-NULL; the other outputs do not depend on that.
+ * The reference's trilinear call (levels 3 and 4) has the same depth in and out and is this operation slice by slice.
+ * One launch, offsets in 64 bits; no tensor of the output's resolution with S slices exists unless prob is asked for.
+ * Arguments are checked before any HIP call; H < h or W < w (shrinking) is an argument error. */
+int aadff_dfv_head_fwd(const float* cost, const float* foc_dists, float* pred, float* std, float* prob_or_null, int B, int S, int h,
+                       int w, int H, int W, aadff_stream_t stream);
+
+/* Gradients of pred above for the cotangent g_pred [B,1,H,W] (std and prob carry none): with dz_s = p_s (foc_dists[b,s] - pred) g,
+ *   d_cost [B,S,h,w] = sum over the output pixels that read a cell of their weight times dz_s;   d_foc [B,S] = sum_pixels p_s g.
+ * The softmax is recomputed from the cost; nothing of the forward is needed.  Gather form, no atomics: the pixels of a cell come from
+ * the forward's own float32 index function, d_cost is summed along x into a scratch [B,S,H,w] and then along y, d_foc in two stages
+ * of fixed order - bitwise reproducible.  A gradient whose pointer is NULL is not computed (both NULL is an error); the other does
+ * not depend on that.  `workspace`: device memory of at least
+ *   4 * B * S * ((d_cost ? H * w : 0) + (d_foc ? ceil(H / R) * ceil(w / TC) : 0)) bytes, with
+ *   ratio = ceil(W / w), TC = clamp(240 / ratio - 1, 1, 8), R = clamp(256 / ((TC + 1) * ratio + 1), 1, 8) in integer arithmetic:
+ *   the cells of a row and the output rows one workgroup of the first stage owns. */
+int aadff_dfv_head_bwd(const float* cost, const float* foc_dists, const float* g_pred, float* d_cost_or_null, float* d_foc_or_null,
+                       void* workspace, size_t workspace_bytes, int B, int S, int h, int w, int H, int W, aadff_stream_t stream);
+
 /* ---- evaluation metrics (csrc/metrics.hip): the depth scores of the reference's dff/metrics.py and the PSNR / SSIM of
  * its batch_PSNR / batch_SSIM as per-image float64 sums that stay on the device.  No atomics: two fixed-order stages through the
  * caller's workspace, bitwise reproducible. */
