@@ -110,6 +110,8 @@ PROTOTYPES = {
     "aadff_dff_loss_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "aadff_dfv_head_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "aadff_dfv_head_bwd": [_P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _P],
+    "aadff_depth_refine_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P],
+    "aadff_depth_refine_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _F, _F, _P],
     "aadff_depth_metric_sums": [_P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _P],
     "aadff_image_metric_sums": [_P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _P],
     "aadff_quantise_u8_host": [_P, _P, _L],

@@ -14,6 +14,9 @@ public function in aadff/dfocus.py).  `attention_depth` and `dff_loss_sums` are 
 stack's scores and the sums of its loss, each with a backward op of its own (csrc/focus_head.hip; public functions in aadff/focus_head.py).
 `dfv_regress` is the head of the reference's second network: a low-resolution cost volume upsampled, softmaxed and regressed to depth and
 its standard deviation in one kernel, with a gather-form backward (csrc/dfv_head.hip; public functions in aadff/dfv_head.py).
+`depth_refine` is the step after any of these estimators: one iteration of a confidence-weighted joint bilateral filter guided by the
+all-in-focus image, with a two-pass gather backward to the filtered quantity and its confidence (csrc/depth_refine.hip; public functions
+in aadff/refine.py).
 `depth_metric_sums` and `image_metric_sums` score the result: the per-image sums behind the reference's depth metrics and PSNR / SSIM
 (csrc/metrics.hip; public functions in aadff/metrics.py); their outputs carry no graph.
 
@@ -719,6 +722,83 @@ def _dfv_backward(ctx, g_pred, g_std, g_prob):
 
 
 dfv_regress.register_autograd(_dfv_backward, setup_context=_dfv_setup)
+
+
+# ---------------------------------------------------------------- confidence-guided depth refinement (csrc/depth_refine.hip)
+def depth_refine_constants(channels, sigma_space, sigma_range):
+    """(ks, kr) = (1 / (2 sigma_space^2), 1 / (2 sigma_range^2 C)), formed in float64 and rounded to the float32 values the kernels get."""
+    return (C.c_float(1.0 / (2.0 * float(sigma_space) ** 2)).value, C.c_float(1.0 / (2.0 * float(sigma_range) ** 2 * channels)).value)
+
+
+def depth_refine_bwd_workspace_bytes(N, H, W):
+    """Bytes of device workspace aadff_depth_refine_bwd needs: alpha, u', beta and the pass-through term, [N,H,W] each."""
+    return 16 * N * H * W
+
+
+@custom_op("aadff::depth_refine", mutates_args=(), device_types="cuda")
+def depth_refine(u: torch.Tensor, c: torch.Tensor, g: torch.Tensor, radius: int, sigma_space: float,
+                 sigma_range: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(u' [N,1,H,W], c' [N,1,H,W]): one iteration of the confidence-weighted joint bilateral filter of u [N,1,H,W] with confidence
+    c [N,1,H,W] and guide g [N,C,H,W], C in 1..4, over the clipped (2 radius + 1)^2 window.  Autograd formula for u and
+    c; the guide is a constant."""
+    N, Cn, H, W = g.shape
+    x, cc, gg = u.contiguous().float(), c.contiguous().float(), g.contiguous().float()
+    ks, kr = depth_refine_constants(Cn, sigma_space, sigma_range)
+    u_out, c_out = torch.empty_like(x), torch.empty_like(cc)
+    with torch.cuda.device(x.device):
+        _abi.call("aadff_depth_refine_fwd", _abi.ptr(x), _abi.ptr(cc), _abi.ptr(gg), _abi.ptr(u_out), _abi.ptr(c_out), N, Cn, H, W,
+                  radius, ks, kr, _st(x))
+    return u_out, c_out
+
+
+@depth_refine.register_fake
+def _(u, c, g, radius, sigma_space, sigma_range):
+    return (torch.empty_like(u, dtype=torch.float32, memory_format=torch.contiguous_format),
+            torch.empty_like(c, dtype=torch.float32, memory_format=torch.contiguous_format))
+
+
+@custom_op("aadff::depth_refine_bwd", mutates_args=(), device_types="cuda")
+def depth_refine_bwd(u: torch.Tensor, c: torch.Tensor, g: torch.Tensor, g_u: torch.Tensor, g_c: torch.Tensor, radius: int,
+                     sigma_space: float, sigma_range: float, need_u: bool, need_c: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(d_u, d_c) [N,1,H,W] of depth_refine for the cotangents g_u, g_c of its two outputs; the sums of the forward are recomputed.  A
+    gradient that is not needed is not written and comes back empty; the other does not depend on that."""
+    N, Cn, H, W = g.shape
+    x, cc, gg = u.contiguous().float(), c.contiguous().float(), g.contiguous().float()
+    gu, gc = g_u.contiguous().float(), g_c.contiguous().float()
+    ks, kr = depth_refine_constants(Cn, sigma_space, sigma_range)
+    d_u = torch.empty_like(x) if need_u else x.new_empty((0,))
+    d_c = torch.empty_like(cc) if need_c else x.new_empty((0,))
+    nbytes = depth_refine_bwd_workspace_bytes(N, H, W)
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _abi.call("aadff_depth_refine_bwd", _abi.ptr(x), _abi.ptr(cc), _abi.ptr(gg), _abi.ptr(gu), _abi.ptr(gc),
+                  _abi.ptr(d_u) if need_u else None, _abi.ptr(d_c) if need_c else None, _abi.ptr(ws), C.c_size_t(nbytes), N, Cn, H, W,
+                  radius, ks, kr, _st(x))
+    return d_u, d_c
+
+
+@depth_refine_bwd.register_fake
+def _(u, c, g, g_u, g_c, radius, sigma_space, sigma_range, need_u, need_c):
+    e = lambda: u.new_empty((0,), dtype=torch.float32)         # noqa: E731  (one each: outputs must not alias)
+    return (torch.empty_like(u, dtype=torch.float32, memory_format=torch.contiguous_format) if need_u else e(),
+            torch.empty_like(c, dtype=torch.float32, memory_format=torch.contiguous_format) if need_c else e())
+
+
+def _refine_setup(ctx, inputs, output):
+    u, c, g, ctx.radius, ctx.sigma_space, ctx.sigma_range = inputs
+    ctx.save_for_backward(u, c, g)
+
+
+def _refine_backward(ctx, g_u, g_c):
+    u, c, g = ctx.saved_tensors
+    need = ctx.needs_input_grad[:2]
+    if not any(need):
+        return None, None, None, None, None, None
+    d_u, d_c = torch.ops.aadff.depth_refine_bwd(u, c, g, g_u, g_c, ctx.radius, ctx.sigma_space, ctx.sigma_range, *need)
+    return ((d_u.reshape(u.shape) if need[0] else None), (d_c.reshape(c.shape) if need[1] else None), None, None, None, None)
+
+
+depth_refine.register_autograd(_refine_backward, setup_context=_refine_setup)
 
 
 # ---------------------------------------------------------------- evaluation metrics (csrc/metrics.hip)

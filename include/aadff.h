@@ -321,6 +321,30 @@ int aadff_dfv_head_fwd(const float* cost, const float* foc_dists, float* pred, f
 int aadff_dfv_head_bwd(const float* cost, const float* foc_dists, const float* g_pred, float* d_cost_or_null, float* d_foc_or_null,
                        void* workspace, size_t workspace_bytes, int B, int S, int h, int w, int H, int W, aadff_stream_t stream);
 
+/* ---- confidence-guided depth refinement (csrc/depth_refine.hip): one iteration of a confidence-weighted joint
+ * bilateral filter.  u [N,1,H,W] the quantity to filter (in practice 1 / depth), c [N,1,H,W] its confidence (c < 2^-30, negative or nan
+ * counts as 0), g [N,C,H,W] the guide, C in 1..4; radius r in 1..8.  For a pixel p and every pixel q of the (2r+1)^2 window clipped to
+ * the image (no padding: a tap outside does not exist), in float32:
+ *   w(p,q) = expf(max(-((dy^2 + dx^2) ks + sum_ch (g(p) - g(q))^2 kr), -64)),   ks = 1 / (2 sigma_space^2), kr = 1 / (2 sigma_range^2 C);
+ *   A = sum w c(q) u(q),  D = sum w c(q), both without the taps whose c(q) is 0 (a u there may be anything, nan included),  Wn = sum w;
+ *   u_out(p) = A / D where D > 0, else u(p) bit for bit;   c_out(p) = D / Wn.
+ * D = 0 means that every confidence of the window is 0: the clamp keeps every weight a normal number.  One launch, offsets in 64 bits.
+ * No output may be one of the inputs or the other output.  Arguments are checked before any HIP call. */
+int aadff_depth_refine_fwd(const float* u, const float* c, const float* g, float* u_out, float* c_out, int N, int C, int H, int W,
+                           int radius, float ks, float kr, aadff_stream_t stream);
+
+/* Gradients of the above for the cotangents g_u_out, g_c_out [N,1,H,W] of u_out and c_out, the guide held constant, u finite:
+ *   alpha(p) = g_u_out(p) / D(p) (0 where D = 0),   beta(p) = g_c_out(p) / Wn(p),
+ *   d_u(q) = c(q) sum_p w(p,q) alpha(p) + [D(q) = 0] g_u_out(q),
+ *   d_c(q) = sum_p w(p,q) (alpha(p) (u(q) - u_out(p)) + beta(p)),   p over the clipped window of q.
+ * The threshold on c is transparent to d_c (the formula holds at every q, also where c(q) counts as 0).  Two gather passes, no
+ * atomics, bitwise reproducible: the first recomputes D, Wn and u_out (nothing of the forward is kept) and writes alpha, u_out, beta
+ * and the pass-through term into `work`, the second gathers them with the same weights.  A gradient whose pointer is NULL is not
+ * written (both NULL is an error); the other does not depend on that.  `work`: device memory of at least 16 * N * H * W bytes. */
+int aadff_depth_refine_bwd(const float* u, const float* c, const float* g, const float* g_u_out, const float* g_c_out, float* d_u_or_null,
+                           float* d_c_or_null, void* work, size_t work_bytes, int N, int C, int H, int W, int radius, float ks, float kr,
+                           aadff_stream_t stream);
+
 /* ---- evaluation metrics (csrc/metrics.hip): the depth scores of the reference's dff/metrics.py and the PSNR / SSIM of
  * its batch_PSNR / batch_SSIM as per-image float64 sums that stay on the device.  No atomics: two fixed-order stages through the
  * caller's workspace, bitwise reproducible. */
