@@ -10,6 +10,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 #include <hip/hip_ext.h>
 #include "common.h"
 
@@ -605,30 +607,22 @@ __device__ __forceinline__ void sphere_step2_from_point(const SphereP& s, Ray2& 
 }
 #endif
 // stop / asphere, forward (the general code of react2 with the margin form of validity)
-__device__ __forceinline__ void other_step2(const aadff_surface_t& s, Ray2& r, f2& vm, int& nan_flag) {
+__device__ __forceinline__ void stop_step2(const aadff_surface_t& s, Ray2& r, f2& vm) {
     const f2 t0 = (s.d - r.oz) * vrcp(r.dz);
     r.ox += r.dx * t0; r.oy += r.dy * t0;
-    if (s.kind == AADFF_SURF_STOP) {
-        r.oz = f2s(s.d);
-        vm = vmin3(vm, s.r * s.r - (r.ox * r.ox + r.oy * r.oy), vm);    // sqrt(x^2+y^2) <= r (surfaces.py:418)
-        if (s.refract_fwd) {
-            const i2 v = refract_dir2(s, r, true, f2s(0.f), f2s(0.f), f2s(-1.f));
-            vm = vsel(v, vm, f2s(-1.f));
-        }
-        return;
+    r.oz = f2s(s.d);
+    vm = vmin3(vm, s.r * s.r - (r.ox * r.ox + r.oy * r.oy), vm);        // sqrt(x^2+y^2) <= r (surfaces.py:418)
+    if (s.refract_fwd) {
+        const i2 v = refract_dir2(s, r, true, f2s(0.f), f2s(0.f), f2s(-1.f));
+        vm = vsel(v, vm, f2s(-1.f));
     }
+}
+__device__ __forceinline__ void asphere_step2(const aadff_surface_t& s, Ray2& r, f2& vm, int& nan_flag) {
+    const f2 t0 = (s.d - r.oz) * vrcp(r.dz);
+    r.ox += r.dx * t0; r.oy += r.dy * t0;
     f2 tau, g;
     i2 valid;
     const i2 alive = vm >= 0.f;
-    if (s.kind == AADFF_SURF_SPHERIC) {                                 // only with -DAADFF_SPHERE_NEWTON-style builds; kept general
-        const i2 hit = conic_root2<true>(s, r, tau);
-        valid = hit & (t0 + tau >= 0.f);
-        r.ox += r.dx * tau; r.oy += r.dy * tau; r.oz = s.d + r.dz * tau;
-        valid &= (r.ox * r.ox + r.oy * r.oy) <= s.r2;
-        const i2 v = refract_dir2(s, r, true, s.c * r.ox, s.c * r.oy, (s.c * r.dz) * tau - 1.f);
-        vm = vsel(valid & v, vm, f2s(-1.f));
-        return;
-    }
 #ifndef AADFF_NORMAL_REEVAL
     newton2(s, r, alive, t0, tau, valid, nan_flag, &g);
     r.ox += r.dx * tau; r.oy += r.dy * tau; r.oz = s.d + r.dz * tau;
@@ -644,7 +638,84 @@ __device__ __forceinline__ void other_step2(const aadff_surface_t& s, Ray2& r, f
     valid &= refract_dir2(s, r, true, nx, ny, -inv);
     vm = vsel(valid, vm, f2s(-1.f));
 }
+__device__ __forceinline__ void other_step2(const aadff_surface_t& s, Ray2& r, f2& vm, int& nan_flag) {
+    if (s.kind == AADFF_SURF_STOP) {
+        stop_step2(s, r, vm);
+    } else if (s.kind == AADFF_SURF_SPHERIC) {                          // only with -DAADFF_SPHERE_NEWTON-style builds; kept general
+        const f2 t0 = (s.d - r.oz) * vrcp(r.dz);
+        r.ox += r.dx * t0; r.oy += r.dy * t0;
+        f2 tau;
+        const i2 hit = conic_root2<true>(s, r, tau);
+        i2 valid = hit & (t0 + tau >= 0.f);
+        r.ox += r.dx * tau; r.oy += r.dy * tau; r.oz = s.d + r.dz * tau;
+        valid &= (r.ox * r.ox + r.oy * r.oy) <= s.r2;
+        const i2 v = refract_dir2(s, r, true, s.c * r.ox, s.c * r.oy, (s.c * r.dz) * tau - 1.f);
+        vm = vsel(valid & v, vm, f2s(-1.f));
+    } else {
+        asphere_step2(s, r, vm, nan_flag);
+    }
+}
+__device__ __forceinline__ SphereP sphere_params(csurf_t cs, int i) {
+    SphereP p;
+    p.d = cs[i].d; p.c = cs[i].c; p.r2 = cs[i].r2; p.eta = cs[i].eta_fwd; p.eta2 = cs[i].eta_fwd2;
+    p.thr = __builtin_bit_cast(float, __builtin_bit_cast(int, cs[i].cos2_min_fwd) + 1);
+    return p;
+}
+// ---- the same trace with the surface kinds known at compile time ----------------------------------------------------
+// In the loop of trace_part2 the ray is carried across a run-time dispatch on `kind`, and the compiler joins the code paths
+// with blocks of register copies at every change of kind (7 into a sphere run, 22-31 out of a run, a stop or an asphere).
+// With the kind sequence a template argument the steps follow each other as straight-line code and the ray stays in one
+// set of registers from the first surface to the last; every number (c, d, r2, eta, k, ai, whether the stop refracts, ...)
+// is still read from the table.  psf_points_dispatch picks the instantiation once per workgroup.
+template <int... K>
+struct KindSeq {
+    static constexpr int n = sizeof...(K);
+    static constexpr int kind(int i) { constexpr int k[] = {K...}; return k[i]; }
+    static constexpr int stop() { for (int i = 0; i < n; ++i) if (kind(i) == AADFF_SURF_STOP) return i; return -1; }
+    static constexpr int split = stop() < 0 ? n / 2 : (stop() + 2 < n ? stop() + 2 : n);     // as psf_points_body computes it
+};
+struct KindLoop { static constexpr int n = 0; };                        // kinds read at run time: trace_part2
+#if defined(AADFF_PSF_GENERIC_LOOP) || defined(AADFF_PSF_SWITCH_LOOP) || defined(AADFF_PSF_SCALAR) || defined(AADFF_PSF_NO_COMPACT) || \
+    defined(AADFF_SPHERE_FROM_POINT)
+#define AADFF_PSF_NO_SEQ 1                                              // measurement builds keep the one loop
+#endif
+namespace seq {
+constexpr int S = AADFF_SURF_SPHERIC, T = AADFF_SURF_STOP, A = AADFF_SURF_ASPHERIC;
+typedef KindSeq<S, S, S, S, S, T, S, S, A, A, S, S> Rf50mm;             // rf50mm, rf50mm_ai4, rf50mm_named
+typedef KindSeq<S, S, S, S, S, S, T, S, S, S, S> F28;                   // 50mm_f2.8
+}
+template <class SEQ, int I, int LAST>
+__device__ __forceinline__ void seq_steps2(const aadff_surface_t* __restrict__ surf, Ray2& r, f2& vm, int& nan_flag) {
+    if constexpr (I < LAST) {
+        if constexpr (SEQ::kind(I) == AADFF_SURF_SPHERIC) sphere_step2(sphere_params((csurf_t)surf, I), r, vm);
+        else if constexpr (SEQ::kind(I) == AADFF_SURF_STOP) stop_step2(surf[I], r, vm);
+        else asphere_step2(surf[I], r, vm, nan_flag);
+        seq_steps2<SEQ, I + 1, LAST>(surf, r, vm, nan_flag);
+    }
+}
+template <class SEQ, int I = 0>
+__device__ __forceinline__ bool seq_matches(csurf_t cs, int n_surf) {
+    if constexpr (I == 0) { if (n_surf != SEQ::n) return false; }
+    if constexpr (I < SEQ::n) return cs[I].kind == SEQ::kind(I) && seq_matches<SEQ, I + 1>(cs, n_surf);
+    else return true;
+}
+// 0: the loop; 1, 2: the compiled sequences.  Wave-uniform: table reads only.
+__device__ __forceinline__ int psf_seq_path(const aadff_surface_t* main_tab, const aadff_surface_t* chief_tab, int n_surf, int force_loop) {
+#ifndef AADFF_PSF_NO_SEQ
+    if (force_loop) return 0;
+    const csurf_t m = (csurf_t)main_tab, c = (csurf_t)(chief_tab ? chief_tab : main_tab);
+    if (seq_matches<seq::Rf50mm>(m, n_surf) && seq_matches<seq::Rf50mm>(c, n_surf)) return 1;
+    if (seq_matches<seq::F28>(m, n_surf) && seq_matches<seq::F28>(c, n_surf)) return 2;
+#endif
+    return 0;
+}
 // surfaces [first, last) forward; r.alive in/out (r.ra not touched)
+template <class SEQ, int FIRST, int LAST>
+__device__ __forceinline__ void trace_seq2(const aadff_surface_t* __restrict__ surf, Ray2& r, int& nan_flag) {
+    f2 vm = vsel(r.alive, f2s(3e38f), f2s(-1.f));
+    seq_steps2<SEQ, FIRST, LAST>(surf, r, vm, nan_flag);
+    r.alive = vm >= 0.f;
+}
 __device__ __forceinline__ void trace_part2(const aadff_surface_t* __restrict__ surf, int first, int last, Ray2& r, int& nan_flag) {
 #ifdef AADFF_PSF_SWITCH_LOOP
     for (int i = first; i < last; ++i) react2(surf[i], r, true, nan_flag);
@@ -657,9 +728,7 @@ __device__ __forceinline__ void trace_part2(const aadff_surface_t* __restrict__ 
     while (i < last) {
         if (cs[i].kind == AADFF_SURF_SPHERIC) {
             do {
-                SphereP cur;
-                cur.d = cs[i].d; cur.c = cs[i].c; cur.r2 = cs[i].r2; cur.eta = cs[i].eta_fwd; cur.eta2 = cs[i].eta_fwd2;
-                cur.thr = __builtin_bit_cast(float, __builtin_bit_cast(int, cs[i].cos2_min_fwd) + 1);
+                const SphereP cur = sphere_params(cs, i);
 #ifdef AADFF_SPHERE_FROM_POINT
                 if (i == 0) sphere_step2(cur, r, vm);
                 else sphere_step2_from_point(cur, r, vm);
@@ -677,8 +746,10 @@ __device__ __forceinline__ void trace_part2(const aadff_surface_t* __restrict__ 
 #endif
 }
 // in: r.alive; out: r.alive and r.ra = alive ? 1 : 0
+template <class SEQ = KindLoop>
 __device__ __forceinline__ void trace_forward2(const aadff_surface_t* __restrict__ surf, int n_surf, Ray2& r, int& nan_flag) {
-    trace_part2(surf, 0, n_surf, r, nan_flag);
+    if constexpr (SEQ::n == 0) trace_part2(surf, 0, n_surf, r, nan_flag);
+    else trace_seq2<SEQ, 0, SEQ::n>(surf, r, nan_flag);
     r.ra = vsel(r.alive, f2s(1.f), f2s(0.f));
 }
 __device__ __forceinline__ void disc_sample2(f2 u_theta, f2 u_r, float R2, f2& x, f2& y) {
@@ -693,6 +764,7 @@ __device__ __forceinline__ void disc_sample2(f2 u_theta, f2 u_r, float R2, f2& x
 #endif
 }
 // rays from one object point to two pupil samples, then through the lens to the sensor plane
+template <class SEQ = KindLoop>
 __device__ __forceinline__ Ray2 trace_pair_to_sensor(float px, float py, float pz, f2 tx, f2 ty, float tz, i2 active,
                                                      const aadff_surface_t* __restrict__ surf, int n_surf, float d_sensor,
                                                      int& nan_flag) {
@@ -702,7 +774,7 @@ __device__ __forceinline__ Ray2 trace_pair_to_sensor(float px, float py, float p
     const f2 inv = vrsq(vmax(r.dx * r.dx + r.dy * r.dy + r.dz * r.dz, f2s(1e-24f)));
     r.dx *= inv; r.dy *= inv; r.dz *= inv;
     r.alive = active;
-    trace_forward2(surf, n_surf, r, nan_flag);
+    trace_forward2<SEQ>(surf, n_surf, r, nan_flag);
     const f2 t = (d_sensor - r.oz) * vrcp(r.dz);
     r.ox += r.dx * t; r.oy += r.dy * t; r.oz += r.dz * t;
     return r;
@@ -898,8 +970,32 @@ __device__ __forceinline__ void normalise_and_write(const float* hist, float* re
     }
 }
 
+// the workgroup's static LDS, declared once per kernel: psf_points_body is instantiated per kind sequence
+struct PsfLds {
+    float* red;
+    int* stage_late;
+#if !defined(AADFF_PSF_SCALAR) && !defined(AADFF_PSF_NO_COMPACT)
+    float (*cbuf)[kCompactMax];
+    unsigned short* cidx;
+    int* c_count;
+#endif
+};
 template <bool EDGE>
-__device__ __forceinline__ void psf_points_body(const float* __restrict__ points, int N, int L,
+__device__ __forceinline__ PsfLds psf_lds() {
+    __shared__ float red[(EDGE ? 5 : 3) * kPsfWaves];
+    __shared__ int stage_late;
+#if !defined(AADFF_PSF_SCALAR) && !defined(AADFF_PSF_NO_COMPACT)
+    __shared__ float cbuf[6][kCompactMax];               // survivors of the first surfaces: origin and direction
+    __shared__ unsigned short cidx[EDGE ? kCompactMax : 1];   // EDGE: and which sample each of them is
+    __shared__ int c_count;
+    return {red, &stage_late, cbuf, cidx, &c_count};
+#else
+    return {red, &stage_late};
+#endif
+}
+
+template <bool EDGE, class SEQ>
+__device__ __forceinline__ void psf_points_body(const PsfLds& lds, const float* __restrict__ points, int N, int L,
                                                           const aadff_surface_t* __restrict__ surf_main,
                                                           const aadff_surface_t* __restrict__ surf_chief,
                                                           aadff_lens_const_t lc,
@@ -909,12 +1005,12 @@ __device__ __forceinline__ void psf_points_body(const float* __restrict__ points
                                                           int spp_chief, long chief_ss, long chief_sl, SplatGeom g, int centre_mode, int map_grid, float* psf,
                                                           float* centre_out, int* flags, StageArgs stage, const EdgeArgs& edge) {
     extern __shared__ float hist[];                      // ks * ks floats (dynamic: ks up to AADFF_MAX_KS = 51)
-    __shared__ float red[(EDGE ? 5 : 3) * kPsfWaves];
-    __shared__ int stage_late;
+    float* const red = lds.red;
+    int& stage_late = *lds.stage_late;
 #if !defined(AADFF_PSF_SCALAR) && !defined(AADFF_PSF_NO_COMPACT)
-    __shared__ float cbuf[6][kCompactMax];               // survivors of the first surfaces: origin and direction
-    __shared__ unsigned short cidx[EDGE ? kCompactMax : 1];   // EDGE: and which sample each of them is
-    __shared__ int c_count;
+    float (*const cbuf)[kCompactMax] = lds.cbuf;
+    unsigned short* const cidx = lds.cidx;
+    int& c_count = *lds.c_count;
 #endif
     const int n = blockIdx.x, l = blockIdx.y;
     int s = blockIdx.z;
@@ -990,7 +1086,7 @@ __device__ __forceinline__ void psf_points_body(const float* __restrict__ points
             // (EDGE: the stack's uniforms are a block the host re-uploads to one address: coherent loads, common.h: fresh)
             disc_sample2(EDGE ? (f2){fresh(ut + i), fresh(ut + j1)} : (f2){ut[i], ut[j1]}, EDGE ? (f2){fresh(ur + i), fresh(ur + j1)} : (f2){ur[i], ur[j1]},
                          lc.enp_r2_shrunk, x2, y2);
-            const Ray2 r = trace_pair_to_sensor(px, py, depth, x2, y2, lc.enp_z, act, surf_chief, lc.n_surf, st.d_sensor, nan_flag);
+            const Ray2 r = trace_pair_to_sensor<SEQ>(px, py, depth, x2, y2, lc.enp_z, act, surf_chief, lc.n_surf, st.d_sensor, nan_flag);
             const f2 wx = r.ox * r.ra, wy = r.oy * r.ra;
             sx += wx.x + wx.y; sy += wy.x + wy.y; sw += r.ra.x + r.ra.y;
             if (EDGE) {
@@ -1040,9 +1136,10 @@ __device__ __forceinline__ void psf_points_body(const float* __restrict__ points
 
     const aadff_surface_t* tab = surf_main + (size_t)l * lc.n_surf;
 #if !defined(AADFF_PSF_SCALAR) && !defined(AADFF_PSF_NO_COMPACT)
-    int split = lc.n_surf / 2;                            // compaction point: two surfaces behind the stop
-    for (int i = 0; i < lc.n_surf; ++i)
-        if (tab[i].kind == AADFF_SURF_STOP) { split = min(i + 2, lc.n_surf); break; }
+    [[maybe_unused]] int split = lc.n_surf / 2;           // compaction point: two surfaces behind the stop (KindSeq::split)
+    if constexpr (SEQ::n == 0)
+        for (int i = 0; i < lc.n_surf; ++i)
+            if (tab[i].kind == AADFF_SURF_STOP) { split = min(i + 2, lc.n_surf); break; }
 #endif
     const float* ut = u_main + (size_t)s * main_ss + (size_t)l * main_sl;
     const float* ur = ut + spp;
@@ -1068,7 +1165,8 @@ __device__ __forceinline__ void psf_points_body(const float* __restrict__ points
             const f2 inv = vrsq(vmax(r.dx * r.dx + r.dy * r.dy + r.dz * r.dz, f2s(1e-24f)));
             r.dx *= inv; r.dy *= inv; r.dz *= inv;
             r.alive = act;
-            trace_part2(tab, 0, split, r, nan_flag);
+            if constexpr (SEQ::n == 0) trace_part2(tab, 0, split, r, nan_flag);
+            else trace_seq2<SEQ, 0, SEQ::split>(tab, r, nan_flag);
             // append the survivors: one LDS atomic per wave, slots by ballot prefix
             const unsigned long long bx = __ballot(r.alive.x != 0), by = __ballot(r.alive.y != 0);
             const int nx = __popcll(bx), ny = __popcll(by);
@@ -1096,7 +1194,8 @@ __device__ __forceinline__ void psf_points_body(const float* __restrict__ points
             r.ox = (f2){cbuf[0][k0], cbuf[0][k1]}; r.oy = (f2){cbuf[1][k0], cbuf[1][k1]}; r.oz = (f2){cbuf[2][k0], cbuf[2][k1]};
             r.dx = (f2){cbuf[3][k0], cbuf[3][k1]}; r.dy = (f2){cbuf[4][k0], cbuf[4][k1]}; r.dz = (f2){cbuf[5][k0], cbuf[5][k1]};
             r.alive = (i2){-1, two ? -1 : 0};
-            trace_part2(tab, split, lc.n_surf, r, nan_flag);
+            if constexpr (SEQ::n == 0) trace_part2(tab, split, lc.n_surf, r, nan_flag);
+            else trace_seq2<SEQ, SEQ::split, SEQ::n>(tab, r, nan_flag);
             const f2 t = (st.d_sensor - r.oz) * vrcp(r.dz);
             r.ox += r.dx * t; r.oy += r.dy * t;
             if (!(EDGE && edge_defer(g, edge, r.ox.x, r.oy.x, r.alive.x != 0, cx, cy, s * L + l, n, cidx[EDGE ? k0 : 0])))
@@ -1113,7 +1212,7 @@ __device__ __forceinline__ void psf_points_body(const float* __restrict__ points
         const int j1 = act.y ? i1 : i;
         f2 x2, y2;
         disc_sample2((f2){ut[i], ut[j1]}, (f2){ur[i], ur[j1]}, lc.enp_r2, x2, y2);
-        const Ray2 r = trace_pair_to_sensor(px, py, depth, x2, y2, lc.enp_z, act, tab, lc.n_surf, st.d_sensor, nan_flag);
+        const Ray2 r = trace_pair_to_sensor<SEQ>(px, py, depth, x2, y2, lc.enp_z, act, tab, lc.n_surf, st.d_sensor, nan_flag);
         if (!(EDGE && edge_defer(g, edge, r.ox.x, r.oy.x, r.ra.x > 0.f, cx, cy, s * L + l, n, i))) splat_hit(hist, g, r.ox.x, r.oy.x, r.ra.x, cx, cy);
         if (!(EDGE && edge_defer(g, edge, r.ox.y, r.oy.y, r.ra.y > 0.f, cx, cy, s * L + l, n, j1))) splat_hit(hist, g, r.ox.y, r.oy.y, r.ra.y, cx, cy);
     }
@@ -1138,6 +1237,34 @@ __device__ __forceinline__ void psf_points_body(const float* __restrict__ points
     if (nan_flag && flags) atomicOr(flags, 1);
 }
 
+// One body per kind sequence, chosen once per workgroup.  The kinds are the same in every wavelength's table (only the indices
+// differ); this workgroup's own is the one checked, and the chief table where the chief pass runs.  trace_mode (AADFF_PSF_TRACE):
+// 1 = the loop for every lens; 2 = as 0, and a workgroup that takes a compiled sequence ORs kPsfSeqFlag << (path - 1) into flags.
+constexpr int kPsfSeqFlag = 256;
+__device__ __forceinline__ void psf_points_dispatch(const float* __restrict__ points, int N, int L,
+                                                    const aadff_surface_t* __restrict__ surf_main,
+                                                    const aadff_surface_t* __restrict__ surf_chief,
+                                                    aadff_lens_const_t lc,
+                                                    const aadff_lens_state_t* __restrict__ states,
+                                                    const float* __restrict__ u_main, int spp, long main_ss,
+                                                    long main_sl, const float* __restrict__ u_chief,
+                                                    int spp_chief, long chief_ss, long chief_sl, SplatGeom g, int centre_mode, int map_grid, float* psf,
+                                                    float* centre_out, int* flags, StageArgs stage, int trace_mode) {
+    const PsfLds lds = psf_lds<false>();
+    auto body = [&](auto seq) {
+        psf_points_body<false, decltype(seq)>(lds, points, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_ss, main_sl, u_chief, spp_chief, chief_ss,
+                                              chief_sl, g, centre_mode, map_grid, psf, centre_out, flags, stage, EdgeArgs{});
+    };
+    [[maybe_unused]] const int path = psf_seq_path(surf_main + (size_t)blockIdx.y * lc.n_surf, centre_mode == 1 ? surf_chief : nullptr, lc.n_surf, trace_mode == 1);
+#ifndef AADFF_PSF_NO_SEQ
+    if (trace_mode == 2 && path && flags && threadIdx.x == 0) atomicOr(flags, kPsfSeqFlag << (path - 1));
+    if (path == 1) body(seq::Rf50mm{});
+    else if (path == 2) body(seq::F28{});
+    else
+#endif
+        body(KindLoop{});
+}
+
 // TIMED: the same code under a second name for the launches that carry aadff_time_next_launch's events (see conv.hip)
 template <bool TIMED>
 __global__ __launch_bounds__(kPsfThreads, 6) void psf_points_kernel(const float* __restrict__ points, int N, int L,
@@ -1148,12 +1275,14 @@ __global__ __launch_bounds__(kPsfThreads, 6) void psf_points_kernel(const float*
                                                           const float* __restrict__ u_main, int spp, long main_ss,
                                                           long main_sl, const float* __restrict__ u_chief,
                                                           int spp_chief, long chief_ss, long chief_sl, SplatGeom g, int centre_mode, int map_grid, float* psf,
-                                                          float* centre_out, int* flags, StageArgs stage) {
-    psf_points_body<false>(points, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_ss, main_sl, u_chief, spp_chief, chief_ss, chief_sl, g,
-                           centre_mode, map_grid, psf, centre_out, flags, stage, EdgeArgs{});
+                                                          float* centre_out, int* flags, StageArgs stage, int trace_mode) {
+    psf_points_dispatch(points, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_ss, main_sl, u_chief, spp_chief, chief_ss, chief_sl, g,
+                        centre_mode, map_grid, psf, centre_out, flags, stage, trace_mode);
 }
 
-// the edge-exact form: band rays deferred to aadff_strict_edge_retrace, histograms left unnormalised in edge.raw
+// the edge-exact form: band rays deferred to aadff_strict_edge_retrace, histograms left unnormalised in edge.raw.  It stays on the
+// run-time loop for every lens: with a body per kind sequence its spills went up (scratch 32 -> 40 B, VGPR spills 9 -> 15, SGPR
+// spills 58 -> 137) - over the budget the sequence trace was given, for a kernel outside the headline step.
 __global__ __launch_bounds__(kPsfThreads, 6) void psf_points_edge_kernel(const float* __restrict__ points, int N, int L,
                                                           const aadff_surface_t* __restrict__ surf_main,
                                                           const aadff_surface_t* __restrict__ surf_chief,
@@ -1163,8 +1292,8 @@ __global__ __launch_bounds__(kPsfThreads, 6) void psf_points_edge_kernel(const f
                                                           long main_sl, const float* __restrict__ u_chief,
                                                           int spp_chief, long chief_ss, long chief_sl, SplatGeom g, int centre_mode,
                                                           float* centre_out, int* flags, EdgeArgs edge) {
-    psf_points_body<true>(points, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_ss, main_sl, u_chief, spp_chief, chief_ss, chief_sl, g,
-                          centre_mode, 0, nullptr, centre_out, flags, StageArgs{}, edge);
+    psf_points_body<true, KindLoop>(psf_lds<true>(), points, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_ss, main_sl, u_chief, spp_chief, chief_ss,
+                                    chief_sl, g, centre_mode, 0, nullptr, centre_out, flags, StageArgs{}, edge);
 }
 
 // raw [S*L][N][ks*ks] -> normalised PSFs in either layout of aadff_psf_points (grid: N x L x S)
@@ -1494,6 +1623,14 @@ int aadff_psf_splat(const float* o, const float* ra, const float* centre, int sp
     return 0;
 }
 
+// AADFF_PSF_TRACE, read per launch (tests switch it): "loop" sends every lens through the run-time loop of trace_part2 (1);
+// "mark" leaves the choice alone and has the workgroups that take a compiled sequence say so in the flags word (2: bit 8 the
+// rf50mm sequence, bit 9 the 50mm_f2.8 one - for a caller that passes a flags word of its own, not one raise_psf_flags reads)
+static int psf_trace_mode() {
+    const char* e = getenv("AADFF_PSF_TRACE");
+    return !e ? 0 : strcmp(e, "loop") == 0 ? 1 : strcmp(e, "mark") == 0 ? 2 : 0;
+}
+
 static int psf_points_launch(const float* points, int S, int N, int L, const aadff_surface_t* surf_main,
                      const aadff_surface_t* surf_chief, aadff_lens_const_t lc, const aadff_lens_state_t* states,
                      const float* u_main, int spp, long main_stride_s, long main_stride_l, const float* u_chief,
@@ -1535,18 +1672,19 @@ static int psf_points_launch(const float* points, int S, int N, int L, const aad
         AADFF_CHECK_ARG(u_main >= lo && u_main < hi && (!u_chief || (u_chief >= lo && u_chief < hi)),
                         "psf_points_staged: u_main/u_chief must point into dst_dev[0 .. S*slice_stride)");
     }
+    const int trace_mode = psf_trace_mode();
     hipEvent_t ev0 = g_time_start, ev1 = g_time_stop;                    // aadff_time_next_launch
     g_time_start = g_time_stop = nullptr;
     if (ev0)
         hipExtLaunchKernelGGL(psf_points_kernel<true>, dim3(N, L, sa.src ? S + 1 : S), dim3(kPsfThreads), (size_t)ks * ks * sizeof(float), (hipStream_t)stream,
                               ev0, ev1, 0, points, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_stride_s, main_stride_l, u_chief,
                               spp_chief, chief_stride_s, chief_stride_l, make_splat_geom(lc.pixel_size, ks), centre_mode, map_grid, psf,
-                              centre_out_or_null, flags_or_null, sa);
+                              centre_out_or_null, flags_or_null, sa, trace_mode);
     else
         hipLaunchKernelGGL(psf_points_kernel<false>, dim3(N, L, sa.src ? S + 1 : S), dim3(kPsfThreads), (size_t)ks * ks * sizeof(float), (hipStream_t)stream, points, N, L, surf_main,
                            surf_chief, lc, states, u_main, spp, main_stride_s, main_stride_l, u_chief, spp_chief, chief_stride_s,
                            chief_stride_l, make_splat_geom(lc.pixel_size, ks),
-                           centre_mode, map_grid, psf, centre_out_or_null, flags_or_null, sa);
+                           centre_mode, map_grid, psf, centre_out_or_null, flags_or_null, sa, trace_mode);
     AADFF_CHECK_LAUNCH();
     return 0;
 }

@@ -110,7 +110,7 @@ for k, (v, n, meta) in rows.items():
             if "psf_points_kernel" in r["Name"]:
                 us = float(r["AverageNs"]) / 1e3
         simd_cycles = us * 1e-6 * 2.4e9 * 1024 if us else None          # 256 CUs x 4 SIMDs at the 2.4 GHz peak clock
-        json.dump({"kernel": "psf_points_kernel (S=10, N=121, L=3, spp 2048 + 2048 chief)", "code_sha256": code_sha256("trace.hip"), "source": f"profiles/{tag}_psf_kernel_pmc.csv, profiles/{tag}_kernel_stats.csv",
+        json.dump({"kernel": "psf_points_kernel (S=10, N=121, L=3, spp 2048 + 2048 chief)", "code_sha256": code_sha256("trace.hip"), "source": f"profiles/{tag}_psf_kernel_pmc.csv, profiles/{tag}_{'kernel_stats_1stream' if one(f'{tag}_stats_s1/**/*_kernel_stats.csv') else 'kernel_stats'}.csv",
                    "us_per_launch_rocprof": us, "SQ_INSTS_VALU": v["SQ_INSTS_VALU"], "SQ_ACTIVE_INST_VALU_quadcycles": v.get("SQ_ACTIVE_INST_VALU"),
                    "valu_wave_instructions_per_surface_per_lane": round(v["SQ_INSTS_VALU"] / (178421760 / 128), 1),
                    "note": "a lane carries two rays (packed fp32), so one surface step of a lane = 2 ray-surface steps; 178 421 760 ray-surface steps per launch (SURVEY.md 8d); includes sampling, chief-ray reduction, compaction and splat",
