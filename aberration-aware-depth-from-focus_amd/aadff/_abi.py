@@ -209,15 +209,30 @@ def require_gpu():
     return lib
 
 
+def _fail(lib, name, rc):
+    msg = lib.aadff_last_error().decode(errors="replace")
+    if rc == -1 and ("should be" in msg or "Input image" in msg):
+        raise AssertionError(msg)     # the reference raises AssertionError for these (render_psf.py:43-53)
+    raise RuntimeError(f"{name} failed (rc={rc}): {msg}")
+
+
 def call(name, *args):
     """Invoke an ABI function; raise with the library's message on failure."""
     lib = require_gpu()
     rc = getattr(lib, name)(*args)
     if rc != 0:
-        msg = lib.aadff_last_error().decode(errors="replace")
-        if rc == -1 and ("should be" in msg or "Input image" in msg):
-            raise AssertionError(msg)     # the reference raises AssertionError for these (render_psf.py:43-53)
-        raise RuntimeError(f"{name} failed (rc={rc}): {msg}")
+        _fail(lib, name, rc)
+
+
+def query_bytes(name, *args):
+    """The byte count an `aadff_*_workspace` entry point writes through its last argument.  Host arithmetic: needs the library, not a
+    GPU; fails like `call`."""
+    lib = _lib if _lib is not None else load_library()
+    nbytes = C.c_size_t(0)
+    rc = getattr(lib, name)(*args, C.byref(nbytes))
+    if rc != 0:
+        _fail(lib, name, rc)
+    return nbytes.value
 
 
 class on_device:
@@ -245,8 +260,24 @@ def ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def opt(t):
+    """`ptr`, or NULL for a tensor that is absent or empty: an optional input, or an output that is not wanted."""
+    return None if t is None or t.numel() == 0 else ptr(t)
+
+
+def workspace(ref, nbytes, dtype=torch.float32):
+    """Uninitialised device scratch of at least `nbytes` bytes on the device of `ref`.  Never zero elements: for nbytes = 0 (a backward
+    op called by hand with nothing needed) the ABI gets a valid pointer beside its byte count of 0, not NULL, and reads neither."""
+    return ref.new_empty((max(1, -(-nbytes // dtype.itemsize)),), dtype=dtype)
+
+
 def stream_ptr(device=None):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def f32(t):
+    """`.contiguous().float()`: what every op does to a tensor argument before its pointer is taken."""
+    return t.contiguous().float()
 
 
 def f32c(t, device):

@@ -338,6 +338,21 @@ def test_custom_ops_are_registered_with_shape_functions():
     assert "Tensor(a" in schema and "flags" in schema                      # flags is declared as mutated
 
 
+def test_custom_op_schemas_match_the_recorded_ones(golden_dir):
+    """Every torch.ops.aadff.* op of aadff/ops.py has the schema recorded in tests/golden/ops_schemas.json (written from the commit before
+    the op layer was restructured): no op is missing, none is extra and none changed - argument names, types, defaults, the mutated
+    `flags` and the returns."""
+    from aadff import ops
+    want = json.load(open(os.path.join(golden_dir, "ops_schemas.json")))
+    defined = {f"aadff::{name}" for name, op in vars(ops).items() if isinstance(op, torch.library.CustomOpDef)}
+    registered = {f"aadff::{name}" for name in dir(torch.ops.aadff) if not name.startswith("_") and name != "name"}
+    assert defined == registered == set(want), f"missing {sorted(set(want) - defined)}, extra {sorted((defined | registered) - set(want))}"
+    got = {name: str(getattr(torch.ops.aadff, name.split("::")[1]).default._schema) for name in want}
+    changed = {name: (got[name], want[name]) for name in want if got[name] != want[name]}
+    assert not changed, changed
+    assert len(got) == 29 and all(name.startswith("aadff::") for name in got)
+
+
 def test_dff_factory_shims(repo_root):
     """dff.factory.get_lens / get_dataset and dff.utils.select_focus_dist resolve like in 2_aber_aware_dff_aif.py:27-60."""
     from dff.factory import get_dataset, get_lens
