@@ -3,7 +3,7 @@
 The reference's deeplens/render_psf.py is plain torch (F.pad + F.conv2d :12-73, unfold / fold :76-107), so its functions
 are differentiable with respect to the image and the PSF.  `deeplens.render_psf` of this package is forward-only; this
 module has the same five functions - signatures, assertions and return conventions of the reference - with gradients
-to the image AND the PSF from hand-written HIP kernels (csrc/conv_bwd.hip through torch.ops.aadff.*_diff, aadff/ops.py):
+to the image AND the PSF from hand-written HIP kernels (csrc/conv_bwd.hip, csrc/gather.hip through torch.ops.aadff.*_diff, aadff/ops.py):
 
     from aadff.diffrender import render_psf_map          # instead of: from deeplens.render_psf import render_psf_map
 
@@ -18,7 +18,7 @@ fused kernel's forward, and a fused backward that recomputes it and runs the tra
 
 `thinlens_render` / `thinlens_render_stack` are ThinLens.render (deeplens/psfnet.py:549-570, the baseline lens of
 dff.factory.get_lens) and its stack form with the same three gradients: the fused forward kernels, and a fused backward that
-re-evaluates every pixel's Gaussian PSF in the kernel (csrc/thinlens_bwd.hip, torch.ops.aadff.thinlens_render_stack_diff) - no
+re-evaluates every pixel's Gaussian PSF in the kernel (csrc/thinlens.hip, torch.ops.aadff.thinlens_render_stack_diff) - no
 [N,H,W,ks,ks] tensor in either direction.  With them both lens models of dff.factory.get_lens have a differentiable renderer.
 
 Not covered: gradients through the ray tracer and the M1-layered stack.

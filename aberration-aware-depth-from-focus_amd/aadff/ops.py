@@ -9,13 +9,14 @@ A `_diff` op is its plain twin - one shared forward, the same ABI call - with a 
 
 ops                                                   C entry points (aadff_...)                  csrc/             public module
 ----------------------------------------------------  ------------------------------------------  ----------------  ------------------------
-render_psf_map(_stack), render_psf, local_psf_render  the same names                              conv.hip          deeplens/render_psf.py
-thinlens_render                                       thinlens_render                             conv.hip          deeplens/psfnet.py
+render_psf_map(_stack), render_psf                    the same names                              conv.hip          deeplens/render_psf.py
+local_psf_render                                      local_psf_render                            gather.hip        deeplens/render_psf.py
+thinlens_render                                       thinlens_render                             thinlens.hip      deeplens/psfnet.py
 render_psf_map_stack_diff / _bwd                      render_psf_map_stack, ..._bwd(_workspace)   conv_bwd.hip      aadff/diffrender.py
-local_psf_render_diff / _bwd                          local_psf_render, ..._bwd                   conv_bwd.hip      aadff/diffrender.py
+local_psf_render_diff / _bwd                          local_psf_render, ..._bwd                   gather.hip        aadff/diffrender.py
 psfnet_forward, psfnet_render_rgbd                    the same names                              psfnet.hip        deeplens/psfnet.py
 psfnet_render_rgbd_diff / _bwd                        psfnet_render_rgbd, ..._bwd(_workspace)     psfnet_bwd.hip    aadff/diffrender.py
-thinlens_render_stack, ..._diff / _bwd                thinlens_render_stack, ..._bwd(_workspace)  thinlens_bwd.hip  psfnet.py, diffrender.py
+thinlens_render_stack, ..._diff / _bwd                thinlens_render_stack, ..._bwd(_workspace)  thinlens.hip      psfnet.py, diffrender.py
 depth_from_stack                                      depth_from_stack                            dfocus.hip        aadff/dfocus.py
 attention_depth / _bwd, dff_loss_sums, dff_loss_bwd   the same names                              focus_head.hip    aadff/focus_head.py
 dfv_regress / _bwd                                    dfv_head_fwd, dfv_head_bwd                  dfv_head.hip      aadff/dfv_head.py
@@ -177,7 +178,7 @@ def thinlens_render(img: torch.Tensor, depth: torch.Tensor, foc_dist: torch.Tens
     return out
 
 
-# ---------------------------------------------------------------- differentiable image space (csrc/conv_bwd.hip)
+# ---------------------------------------------------------------- differentiable image space (csrc/conv_bwd.hip, csrc/gather.hip)
 # Plain (non-differentiable) ops over the backward ABI, and front ops whose forward is the EXISTING kernel and whose autograd
 # formula calls them.  A gradient that is not needed is not computed (NULL pointer) and comes back as an empty tensor.
 @_fake(lambda img, psf_maps, dy, grid, need_img, need_psf: _grad_pair(img, psf_maps, need_img, need_psf))
@@ -346,7 +347,7 @@ def _rgbd_backward(ctx, dy, _dflags):
 psfnet_render_rgbd_diff.register_autograd(_rgbd_backward, setup_context=_rgbd_setup)
 
 
-# ---------------------------------------------------------------- differentiable thin-lens baseline (csrc/thinlens_bwd.hip)
+# ---------------------------------------------------------------- differentiable thin-lens baseline (csrc/thinlens.hip)
 def _thin_stack_out(img, depth, foc_dists, *_):
     N, Cn, H, W = img.shape
     return img.new_empty((N, Cn, foc_dists.numel() // N, H, W), dtype=torch.float32)

@@ -8,7 +8,7 @@
 namespace aadff {
 
 void set_error(const char* fmt, ...);
-// argument domains of the image-space operators (conv.hip), checked the same way by forward and backward entries
+// argument domains of the image-space operators (conv.hip, gather.hip), checked the same way by forward and backward entries
 int conv_check_shape(int B, int C, int S, int H, int W, int grid, int ks);
 int local_check_shape(int B, int C, int H, int W, int ks);
 
@@ -32,6 +32,10 @@ int local_check_shape(int B, int C, int H, int W, int ks);
 #define AADFF_CHECK_LAUNCH() AADFF_CHECK_HIP(hipGetLastError())
 
 constexpr int kWave = 64;   // gfx950 wavefront
+
+// operand types of __builtin_amdgcn_global_load_lds (global memory -> LDS without passing through VGPRs)
+typedef const __attribute__((address_space(1))) void* lp_gptr_t;
+typedef __attribute__((address_space(3))) void* lp_lptr_t;
 
 // armed by aadff_time_next_launch, consumed (and cleared) by the next slice-batched convolution or PSF-grid launch of the thread
 extern thread_local hipEvent_t g_time_start, g_time_stop;

@@ -1,26 +1,14 @@
 // Image-space PSF application for gfx950 (MI355X): patch-wise PSF-grid convolution
-// (render_psf_map / render_psf, single slice and stack-fused) and per-pixel PSF gather
-// (local_psf_render).  Semantics follow deeplens/render_psf.py of the reference; see
-// include/aadff.h for the per-entry citations and DESIGN.md for the kernel design.
+// (render_psf_map / render_psf, single slice and stack-fused).  Semantics follow
+// deeplens/render_psf.py of the reference; see include/aadff.h for the per-entry citations
+// and DESIGN.md for the kernel design.  (Per-pixel PSF gather: gather.hip.)
 #include <cmath>
-#include <cstdarg>
 #include <cstdlib>
 #include <type_traits>
 #include <hip/hip_ext.h>
 #include "common.h"
 
 namespace aadff {
-
-// ------------------------------------------------------------------------------------
-// error string shared by the whole library
-// ------------------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
 
 // PatchBounds, fill_bounds, the magic-multiplier divisions, xcd_remap and reflect_idx live in common.h (shared with conv_bwd.hip)
 
@@ -664,8 +652,6 @@ __global__ __launch_bounds__(256) void conv_psf_map_toeplitz_wide_kernel(
 // zero-padded tap rows in LDS; a workgroup = NC slice chunks x 2 row groups sharing one staged band of a patch, so
 // the image is read from HBM once for all slices.  Same exact fp16 hi/lo operand split as above.
 // ------------------------------------------------------------------------------------
-typedef const __attribute__((address_space(1))) void* lp_gptr_t;
-typedef __attribute__((address_space(3))) void* lp_lptr_t;
 namespace sb {
 constexpr int KS = 11, PAD = 5;
 constexpr int TCOLS = 96;                 // output columns per workgroup tile (3 column blocks of 32)
@@ -1084,8 +1070,6 @@ __global__ __launch_bounds__(64 * NC, LAYERED ? 4 : 5) void conv_psf_map_sbatch_
 // row: 16-byte stores.  Staging (24-row x 96-column band of one patch and plane, image read as fp32, tile-wide power-of-two
 // scale, exact fp16 hi/lo split) is the slice-batched kernel's; wave w renders column block w of the band (3 groups of 8 rows).
 // ------------------------------------------------------------------------------------
-struct __attribute__((packed, aligned(4))) f4u { float x, y, z, w; };   // 16-byte load / store at 4-byte alignment
-
 namespace blk {
 constexpr int TCOLS = 96, WCOLS = TCOLS + 12, WDW = WCOLS / 2, RB = 24, THP = RB + 10, NW = 3;
 constexpr int RPP = 240, LO = 112;        // row-pair pitch, offset of the lo plane (dwords)
@@ -1611,9 +1595,6 @@ __global__ __launch_bounds__(256) void conv_psf_map_generic_kernel(const float* 
     }
 }
 
-// events armed by aadff_time_next_launch for the next stack-convolution / PSF-grid launch of this host thread (common.h)
-thread_local hipEvent_t g_time_start = nullptr, g_time_stop = nullptr;
-
 template <int KS>
 static int launch_fast(const float* img, const float* psf, float* out, long sbc, long ss, int B, int C, int S, int H, int W,
                        int grid, int ntx, int nty, const PatchBounds& pb, hipStream_t st) {
@@ -1876,335 +1857,11 @@ static int conv_dispatch(const float* img, const float* psf, float* out, long sb
     return 0;
 }
 
-// ------------------------------------------------------------------------------------
-// Per-pixel PSF gather (local_psf_render): HBM-bound on the PSF tensor (ks*ks*4 B/pixel + 24 B/pixel).
-// One wave per run of 64 consecutive pixels of one image row:
-//   * lane l streams ITS pixel's ks*ks taps straight from global memory with 16-byte loads (the taps of
-//     a pixel are contiguous; every byte of every cache line is used, the lines live in L1 for the few
-//     loads that share them) - no LDS round trip for the 484 B/pixel stream, so 8+ waves per CU keep
-//     tens of KB of loads in flight;
-//   * only the C x ks x (64+ks-1) replicate-clamped image window is staged in LDS (read at lane+v:
-//     conflict-free);
-//   * no flip (render_psf.py:99-105 multiplies unfold() patches with the kernel as is).
-// ------------------------------------------------------------------------------------
-
-constexpr int LP_NPX = 64, LP_MAXC = 4;
-
-// Replicate-clamped image window [C][KS][64+KS-1] of one 64-pixel run into LDS.  Every (channel, row) is one coalesced
-// load of 64 floats plus a KS-1 float tail, and ALL of them are issued before the first is written to LDS: as a loop of
-// dependent load -> store iterations this staging was a chain of ~38 memory latencies per run and, not the PSF stream,
-// set the speed of the gather kernels (measured: 196 -> see DESIGN.md).
-template <int KS, int CN, int NWV = 1>      // CN > 0: compile-time channel count (no per-channel branches); CN == 0: runtime C <= LP_MAXC
-__device__ __forceinline__ void lp_stage_window(const float* __restrict__ img, float* tl, int b, int C, int H, int W, int y, int x0, int lane,
-                                                int wave = 0) {                         // NWV waves share the rows: row index % NWV == wave
-    constexpr int PAD = KS / 2, TWD = LP_NPX + KS - 1;
-    constexpr int MC = CN > 0 ? CN : LP_MAXC;
-    float v0[MC * KS], v1[MC * KS];
-    const int xa = min(max(x0 - PAD + lane, 0), W - 1);
-    const int xb = min(max(x0 - PAD + LP_NPX + lane, 0), W - 1);
-#pragma unroll
-    for (int cc = 0; cc < MC; ++cc) {
-        if (CN > 0 || cc < C) {
-#pragma unroll
-            for (int u = 0; u < KS; ++u) {
-                if (NWV > 1 && (cc * KS + u) % NWV != wave) continue;
-                const int yy = min(max(y - PAD + u, 0), H - 1);
-                const float* row = img + ((size_t)(b * C + cc) * H + yy) * W;
-                v0[cc * KS + u] = row[xa];
-                v1[cc * KS + u] = lane < KS - 1 ? row[xb] : 0.f;
-            }
-        }
-    }
-#pragma unroll
-    for (int cc = 0; cc < MC; ++cc) {
-        if (CN > 0 || cc < C) {
-#pragma unroll
-            for (int u = 0; u < KS; ++u) {
-                if (NWV > 1 && (cc * KS + u) % NWV != wave) continue;
-                tl[(cc * KS + u) * TWD + lane] = v0[cc * KS + u];
-                if (lane < KS - 1) tl[(cc * KS + u) * TWD + LP_NPX + lane] = v1[cc * KS + u];
-            }
-        }
-    }
-}
-
-template <int KS, int CN>
-__global__ __launch_bounds__(64) void local_psf_kernel(const float* __restrict__ img, const float* __restrict__ psf,
-                                                        float* __restrict__ out, int C, int H, int W) {
-    constexpr int MC = CN > 0 ? CN : LP_MAXC;
-    constexpr int KK = KS * KS, TWD = LP_NPX + KS - 1;
-    __shared__ float tl[MC * KS * TWD];
-    const int lane = threadIdx.x;
-    const int x0 = blockIdx.x * LP_NPX, y = blockIdx.y, b = blockIdx.z;
-    const int npx = min(LP_NPX, W - x0);
-    const bool act = lane < npx;
-    const float* pp = psf + ((size_t)(b * H + y) * W + x0 + (act ? lane : 0)) * KK;
-
-    // first batch of tap loads is in flight while the image window is staged
-    constexpr int NB = 8;                                    // 16-byte loads per batch
-    constexpr int NV = KK / 4, REM = KK - 4 * NV;            // KK = 4*NV + REM
-    f4u wq[NB];
-#pragma unroll
-    for (int i = 0; i < NB; ++i)
-        if (i < NV) wq[i] = *reinterpret_cast<const f4u*>(pp + 4 * i);
-
-    lp_stage_window<KS, CN>(img, tl, b, C, H, W, y, x0, lane);
-    __syncthreads();
-
-    float acc[MC] = {};
-    auto tap = [&](int t, float wv) {
-        const int u = t / KS, v = t - u * KS;
-#pragma unroll
-        for (int cc = 0; cc < MC; ++cc)
-            if (CN > 0 || cc < C) acc[cc] = fmaf(tl[(cc * KS + u) * TWD + lane + v], wv, acc[cc]);
-    };
-#pragma unroll
-    for (int base = 0; base < NV; base += NB) {
-        f4u cur[NB];
-#pragma unroll
-        for (int i = 0; i < NB; ++i) cur[i] = wq[i];
-#pragma unroll
-        for (int i = 0; i < NB; ++i)                           // next batch goes out before this one is consumed
-            if (base + NB + i < NV) wq[i] = *reinterpret_cast<const f4u*>(pp + 4 * (base + NB + i));
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-            if (base + i < NV) {
-                const int t = 4 * (base + i);
-                tap(t, cur[i].x); tap(t + 1, cur[i].y); tap(t + 2, cur[i].z); tap(t + 3, cur[i].w);
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < REM; ++i) tap(4 * NV + i, pp[4 * NV + i]);
-    if (act) {
-#pragma unroll
-        for (int cc = 0; cc < MC; ++cc)
-            if (CN > 0 || cc < C) out[((size_t)(b * C + cc) * H + y) * W + x0 + lane] = acc[cc];
-    }
-}
-
-// LDS-DMA form (default when the rows are 16-byte aligned: W % 4 == 0).  The taps of a 64-pixel run are ONE contiguous
-// block of 64*ks*ks*4 bytes (30 976 B at ks 11), so the run is fetched by `global_load_lds_dwordx4` wave-instructions of
-// 1 KiB each (64 lanes x 16 consecutive bytes: every request a full line, nothing passes through VGPRs) that are all in
-// flight at once, and each lane then reads ITS pixel's taps from LDS at a pitch of ks*ks dwords (odd: the 32 lanes of a
-// ds_read_b32 group hit 32 different banks).  The old form let every lane walk its own 484-byte row with 16-byte loads:
-// one wave-instruction touched 64 different rows.  One wave per workgroup, 40 KB of LDS -> 4 runs (120 KB) in flight
-// per CU while other workgroups of the CU compute.  A workgroup is 2 or 4 waves that split the pieces, the window rows and the
-// tap rows of the run (partial sums meet through the freed tap buffer): the shorter a workgroup computes, the larger the
-// share of its life it spends with loads in flight.
-#ifndef AADFF_LP_DMA_AUX
-#define AADFF_LP_DMA_AUX 0          // 2 = nt (streamed-once hint)
-#endif
-template <int KS, int CN, int NWV>
-__global__ __launch_bounds__(64 * NWV) void local_psf_dma_kernel(const float* __restrict__ img, const float* __restrict__ psf,
-                                                                  float* __restrict__ out, int C, int H, int W) {
-    constexpr int KK = KS * KS, TWD = LP_NPX + KS - 1;
-    constexpr int RUN_BYTES = LP_NPX * KK * 4, PIECES = (RUN_BYTES + 1023) / 1024;
-    extern __shared__ __attribute__((aligned(16))) float lp_smem[];      // (64*KK + C*KS*TWD) floats: 40 744 B at ks 11, C 3 -> 4 per CU
-    float* wl = lp_smem;
-    float* tl = lp_smem + LP_NPX * KK;
-    const int lane = threadIdx.x & 63;
-    const int wave = NWV > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
-    const int x0 = blockIdx.x * LP_NPX, y = blockIdx.y, b = blockIdx.z;
-    const int npx = min(LP_NPX, W - x0);
-    const int bytes = npx * KK * 4;                          // multiple of 16 (W % 4 == 0)
-    const char* src = reinterpret_cast<const char*>(psf + ((size_t)(b * H + y) * W + x0) * KK);
-#pragma unroll
-    for (int p = 0; p < PIECES; ++p) {
-        if (NWV > 1 && p % NWV != wave) continue;           // the waves of a workgroup share the run's pieces
-        const int off = p * 1024 + lane * 16;
-        if (off < bytes)
-            __builtin_amdgcn_global_load_lds((lp_gptr_t)(src + off), (lp_lptr_t)(reinterpret_cast<char*>(wl) + p * 1024), 16, 0, AADFF_LP_DMA_AUX);
-    }
-    lp_stage_window<KS, CN, NWV>(img, tl, b, C, H, W, y, x0, lane, wave);
-    __syncthreads();                                         // also waits for the DMA pieces (vmcnt(0))
-    constexpr int MC = CN > 0 ? CN : LP_MAXC;
-    const float* wr = wl + lane * KK;
-    float acc[MC] = {};
-    // One wave per SIMD cannot hide LDS latency by occupancy: read a whole tap row (KS taps + MC*KS window values)
-    // into registers in one burst, one row ahead of the FMAs that consume it.  With NWV = 2 the tap rows alternate
-    // between the two waves (half the compute latency per run: the workgroup spends more of its life with loads in flight).
-    auto load_row = [&](int u, float (&w)[KS], float (&x)[MC][KS]) {
-#pragma unroll
-        for (int v = 0; v < KS; ++v) w[v] = wr[u * KS + v];
-#pragma unroll
-        for (int cc = 0; cc < MC; ++cc)
-            if (CN > 0 || cc < C) {
-#pragma unroll
-                for (int v = 0; v < KS; ++v) x[cc][v] = tl[(cc * KS + u) * TWD + lane + v];
-            }
-    };
-    float w0[KS], x0r[MC][KS], w1[KS], x1r[MC][KS];
-    const int ustart = wave;                                 // rows ustart, ustart + NWV, ...
-    if (ustart < KS) load_row(ustart, w0, x0r);
-#pragma unroll
-    for (int k = 0; k < (KS + NWV - 1) / NWV; ++k) {
-        const int u = ustart + k * NWV;
-        if (u >= KS) break;
-        if (u + NWV < KS) {
-            if (k & 1) load_row(u + NWV, w0, x0r); else load_row(u + NWV, w1, x1r);
-        }
-        asm volatile("" ::: "memory");                       // keep the next row's reads ahead of this row's FMAs
-#pragma unroll
-        for (int v = 0; v < KS; ++v) {
-#pragma unroll
-            for (int cc = 0; cc < MC; ++cc)
-                if (CN > 0 || cc < C) acc[cc] = fmaf((k & 1) ? x1r[cc][v] : x0r[cc][v], (k & 1) ? w1[v] : w0[v], acc[cc]);
-        }
-    }
-    if (NWV > 1) {                                           // wave 1 hands its partial sums over through the (now free) tap buffer
-        __syncthreads();
-        if (wave != 0) {
-#pragma unroll
-            for (int cc = 0; cc < MC; ++cc) wl[((wave - 1) * MC + cc) * 64 + lane] = acc[cc];
-        }
-        __syncthreads();
-        if (wave != 0) return;
-#pragma unroll
-        for (int w = 1; w < NWV; ++w)
-#pragma unroll
-            for (int cc = 0; cc < MC; ++cc) acc[cc] += wl[((w - 1) * MC + cc) * 64 + lane];
-    }
-    if (lane >= npx) return;
-#pragma unroll
-    for (int cc = 0; cc < MC; ++cc)
-        if (CN > 0 || cc < C) out[((size_t)(b * C + cc) * H + y) * W + x0 + lane] = acc[cc];
-}
-
-// ------------------------------------------------------------------------------------
-// Thin-lens baseline (ThinLens.coc + ThinLens.render, deeplens/psfnet.py:503-570) with the PSF evaluated IN the gather
-// kernel: per pixel  coc -> Gaussian exp(-(x^2+y^2)/(2 rad^2)) cut at x^2+y^2 < rad^2 -> L1 normalise -> 11x11 gather over
-// the replicate-padded image (render_psf.py:76-107, no flip).  24 B/pixel of HBM traffic + 4 B of depth instead of the
-// 508 B/pixel of materialising the [N,H,W,ks,ks] PSF tensor and streaming it through local_psf_render.
-//   coc chain in the reference's fp32 op order with IEEE divisions (the hard cut r^2 < rad^2 is discontinuous: a 1-ulp
-//   difference in rad^2 next to an integer would flip a whole ring of taps), Gaussian as a product of two 1-D factors
-//   (differs from exp of the sum by rounding only), normalisation folded into one division of the gathered sums.
-// ------------------------------------------------------------------------------------
-template <int KS, int CN>
-__global__ __launch_bounds__(64) void thinlens_kernel(const float* __restrict__ img, const float* __restrict__ depth,
-                                                       const float* __restrict__ foc_dist, const int* __restrict__ negate,
-                                                       float* __restrict__ out, int C, int H, int W, float a_coc, float foc_len,
-                                                       float inv_ps, float d_min, float d_max) {
-    constexpr int MC = CN > 0 ? CN : LP_MAXC;
-    constexpr int PAD = KS / 2, TWD = LP_NPX + KS - 1;
-    __shared__ float tl[MC * KS * TWD];
-    const int lane = threadIdx.x;
-    const int x0 = blockIdx.x * LP_NPX, y = blockIdx.y, b = blockIdx.z;
-    const int npx = min(LP_NPX, W - x0);
-    const bool act = lane < npx;
-    float d = depth[((size_t)b * H + y) * W + x0 + (act ? lane : 0)];
-    float fd = foc_dist[b];
-    lp_stage_window<KS, CN>(img, tl, b, C, H, W, y, x0, lane);
-    __syncthreads();
-    if (negate && *negate) { d = -d; fd = -fd; }            // `if (depth < 0).any()` is a whole-tensor test (psfnet.py:505)
-    d = fminf(fmaxf(d, d_min), d_max);
-    float rad2;
-    {
-#pragma clang fp contract(off)
-        float coc = a_coc * fabsf(d - fd);                   // foc_len / fnum * |depth - foc_dist| / depth * foc_len / (foc_dist - foc_len)
-        coc = coc / d;
-        coc = coc * foc_len;
-        coc = coc / (fd - foc_len);
-        coc = fmaxf(coc * inv_ps, 0.1f);                     // tensor / python-scalar = tensor * (1 / scalar) in ATen
-        const float rad = coc * 0.5f;
-        rad2 = rad * rad;
-    }
-    float e[PAD + 1];                                        // exp(-k^2 / 2 / rad^2), k = 0..PAD
-#pragma unroll
-    for (int k = 0; k <= PAD; ++k) e[k] = __expf((float)(-(k * k)) * 0.5f / rad2);
-    float acc[MC] = {};
-    float wsum = 0.f;
-#pragma unroll
-    for (int u = 0; u < KS; ++u) {
-#pragma unroll
-        for (int v = 0; v < KS; ++v) {
-            const int du = u < PAD ? PAD - u : u - PAD, dv = v < PAD ? PAD - v : v - PAD;
-            const float wv = (float)(du * du + dv * dv) < rad2 ? e[du] * e[dv] : 0.f;
-            wsum += wv;
-#pragma unroll
-            for (int cc = 0; cc < MC; ++cc)
-                if (CN > 0 || cc < C) acc[cc] = fmaf(tl[(cc * KS + u) * TWD + lane + v], wv, acc[cc]);
-        }
-    }
-    if (act) {
-        const float inv = 1.f / wsum;
-#pragma unroll
-        for (int cc = 0; cc < MC; ++cc)
-            if (CN > 0 || cc < C) out[((size_t)(b * C + cc) * H + y) * W + x0 + lane] = acc[cc] * inv;
-    }
-}
-
-// any odd ks / any channel count: PSFs through LDS (the previous design), correctness path
-template <int NPX>
-__global__ __launch_bounds__(64) void local_psf_generic_kernel(const float* __restrict__ img, const float* __restrict__ psf,
-                                                                float* __restrict__ out, int C, int H, int W, int ks) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int kk = ks * ks, pad = ks / 2, tw = NPX + ks - 1;
-    float* wl = smem;                 // [NPX][kk]
-    float* tl = smem + NPX * kk;      // [C][ks][tw]
-    const int lane = threadIdx.x;
-    const int x0 = blockIdx.x * NPX, y = blockIdx.y, b = blockIdx.z;
-    const int npx = min(NPX, W - x0);
-
-    const float* pp = psf + ((size_t)(b * H + y) * W + x0) * kk;
-    for (int e = lane; e < npx * kk; e += kWave) wl[e] = pp[e];
-    for (int e = lane; e < C * ks * tw; e += kWave) {
-        const int cc = e / (ks * tw), rem = e - cc * ks * tw;
-        const int u = rem / tw, xx = rem - u * tw;
-        const int yy = min(max(y - pad + u, 0), H - 1);
-        const int xs = min(max(x0 - pad + xx, 0), W - 1);
-        tl[e] = img[((size_t)(b * C + cc) * H + yy) * W + xs];
-    }
-    __syncthreads();
-    if (lane < npx) {
-        const float* wr = wl + lane * kk;
-        for (int cc = 0; cc < C; ++cc) {
-            const float* tr = tl + cc * ks * tw + lane;
-            float acc = 0.f;
-            for (int u = 0; u < ks; ++u)
-                for (int v = 0; v < ks; ++v) acc = fmaf(tr[u * tw + v], wr[u * ks + v], acc);
-            out[((size_t)(b * C + cc) * H + y) * W + x0 + lane] = acc;
-        }
-    }
-}
-
 }  // namespace aadff
 
 using namespace aadff;
 
-namespace aadff {
-// the shape domain of the per-pixel gather, shared with its backward (conv_bwd.hip)
-int local_check_shape(int B, int C, int H, int W, int ks) {
-    AADFF_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "local_psf_render: empty tensor");
-    AADFF_CHECK_ARG(ks % 2 == 1 && ks >= 1 && ks <= AADFF_MAX_KS, "local_psf_render: ks %d must be odd and <= %d", ks, AADFF_MAX_KS);
-    AADFF_CHECK_ARG(H <= 65535 && B <= 65535, "local_psf_render: H or B too large for the launch grid");
-    if (!(C <= LP_MAXC && (ks == 3 || ks == 5 || ks == 7 || ks == 9 || ks == 11 || ks == 13))) {       // generic kernel: PSFs and window in LDS
-        const int npx = ks <= 15 ? 64 : 16;
-        const size_t lds = ((size_t)npx * ks * ks + (size_t)C * ks * (npx + ks - 1)) * sizeof(float);
-        AADFF_CHECK_ARG(lds <= 160 * 1024, "local_psf_render: C=%d ks=%d needs %zu B of LDS", C, ks, lds);
-    }
-    return 0;
-}
-}  // namespace aadff
-
 extern "C" {
-
-int aadff_abi_version(void) { return AADFF_ABI_VERSION; }
-const char* aadff_last_error(void) { return g_err; }
-
-int aadff_device_info(int* n_cu, int* lds_bytes, char* arch, int arch_len) {
-    int dev = 0;
-    AADFF_CHECK_HIP(hipGetDevice(&dev));
-    hipDeviceProp_t p;
-    AADFF_CHECK_HIP(hipGetDeviceProperties(&p, dev));
-    if (n_cu) *n_cu = p.multiProcessorCount;
-    if (lds_bytes) *lds_bytes = (int)p.sharedMemPerBlock;
-    if (arch && arch_len > 0) {
-        std::strncpy(arch, p.gcnArchName, arch_len - 1);
-        arch[arch_len - 1] = 0;
-    }
-    return 0;
-}
 
 int aadff_render_psf_map(const float* img, const float* psf_map, float* out, int B, int C, int H, int W, int grid,
                          int ks, aadff_stream_t stream) {
@@ -2297,78 +1954,10 @@ extern "C" int aadff_sb_trace_buffer(unsigned long long* dev_buf) {      // not 
 }
 #endif
 
-int aadff_time_next_launch(void* start_event, void* stop_event) {
-    AADFF_CHECK_ARG((start_event == nullptr) == (stop_event == nullptr), "time_next_launch: give both events or neither");
-    g_time_start = (hipEvent_t)start_event;
-    g_time_stop = (hipEvent_t)stop_event;
-    return 0;
-}
-
 int aadff_render_psf(const float* img, const float* psf, float* out, int B, int C, int H, int W, int ks,
                      aadff_stream_t stream) {
     // a 1x1 PSF grid: the [C,ks,ks] PSF is its own map (render_psf.py:12-28 vs :31-73)
     return conv_dispatch(img, psf, out, (long)H * W, (long)H * W, B, C, 1, H, W, 1, ks, (hipStream_t)stream);
-}
-
-int aadff_local_psf_render(const float* img, const float* psf, float* out, int B, int C, int H, int W, int ks,
-                           aadff_stream_t stream) {
-    AADFF_CHECK_ARG(img && psf && out, "local_psf_render: NULL pointer");
-    if (int rc = local_check_shape(B, C, H, W, ks)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (C <= LP_MAXC && (ks == 3 || ks == 5 || ks == 7 || ks == 9 || ks == 11 || ks == 13)) {
-        dim3 g((W + LP_NPX - 1) / LP_NPX, H, B);
-        // LDS-DMA form needs 16-byte aligned runs (rows of W*ks*ks floats, W % 4 == 0); AADFF_LOCAL_PSF=direct forces the
-        // per-lane streaming form for A/B runs
-        static const bool force_direct = [] { const char* e = std::getenv("AADFF_LOCAL_PSF"); return e && e[0] == 'd'; }();
-        const bool dma = !force_direct && W % 4 == 0 && (reinterpret_cast<uintptr_t>(psf) & 15) == 0;
-        const size_t dlds = (size_t)(64 * ks * ks + C * ks * (64 + ks - 1)) * sizeof(float);
-        // waves per workgroup (they split the run's DMA pieces, window rows and tap rows; ks 11 at 1024^2: 1 -> 145 us,
-        // 2 -> 122, 4 -> 101, 8 -> 111; ks 5: 2 -> 25, 4 -> 27): 4 for ks >= 9, 2 below
-#define AADFF_LPC(K, CN) do { constexpr int NWV_ = K >= 9 ? 4 : 2; \
-                              if (dma) hipLaunchKernelGGL((local_psf_dma_kernel<K, CN, NWV_>), g, dim3(64 * NWV_), dlds, st, img, psf, out, C, H, W); \
-                              else hipLaunchKernelGGL((local_psf_kernel<K, CN>), g, dim3(64), 0, st, img, psf, out, C, H, W); } while (0)
-#define AADFF_LP(K) case K: if (C == 3) AADFF_LPC(K, 3); else if (C == 1) AADFF_LPC(K, 1); else AADFF_LPC(K, 0); break;
-        switch (ks) {
-            AADFF_LP(3) AADFF_LP(5) AADFF_LP(7) AADFF_LP(9) AADFF_LP(11) AADFF_LP(13)
-        }
-#undef AADFF_LP
-#undef AADFF_LPC
-    } else {
-        const int npx = ks <= 15 ? 64 : 16;
-        const size_t lds = ((size_t)npx * ks * ks + (size_t)C * ks * (npx + ks - 1)) * sizeof(float);
-        dim3 g((W + npx - 1) / npx, H, B);
-        if (npx == 64) {
-            if (lds > 64 * 1024)
-                AADFF_CHECK_HIP(hipFuncSetAttribute((const void*)local_psf_generic_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(local_psf_generic_kernel<64>, g, dim3(64), lds, st, img, psf, out, C, H, W, ks);
-        } else {
-            if (lds > 64 * 1024)
-                AADFF_CHECK_HIP(hipFuncSetAttribute((const void*)local_psf_generic_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(local_psf_generic_kernel<16>, g, dim3(64), lds, st, img, psf, out, C, H, W, ks);
-        }
-    }
-    AADFF_CHECK_LAUNCH();
-    return 0;
-}
-
-int aadff_thinlens_render(const float* img, const float* depth, const float* foc_dist, const int* negate_or_null, float* out,
-                          int B, int C, int H, int W, int ks, float foc_len_over_fnum, float foc_len, float inv_pixel_size,
-                          float d_min, float d_max, aadff_stream_t stream) {
-    AADFF_CHECK_ARG(img && depth && foc_dist && out, "thinlens_render: NULL pointer");
-    AADFF_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "thinlens_render: empty tensor");
-    AADFF_CHECK_ARG(C <= LP_MAXC, "thinlens_render: at most %d channels", LP_MAXC);
-    AADFF_CHECK_ARG(ks == 3 || ks == 5 || ks == 7 || ks == 9 || ks == 11 || ks == 13, "thinlens_render: ks %d not in {3,5,...,13}", ks);
-    AADFF_CHECK_ARG(H <= 65535 && B <= 65535, "thinlens_render: H or B too large for the launch grid");
-    hipStream_t st = (hipStream_t)stream;
-    dim3 g((W + LP_NPX - 1) / LP_NPX, H, B);
-#define AADFF_TLC(K, CN) hipLaunchKernelGGL((thinlens_kernel<K, CN>), g, dim3(64), 0, st, img, depth, foc_dist, negate_or_null, out, C, H, W, \
-                                            foc_len_over_fnum, foc_len, inv_pixel_size, d_min, d_max)
-#define AADFF_TL(K) case K: if (C == 3) AADFF_TLC(K, 3); else AADFF_TLC(K, 0); break;
-    switch (ks) { AADFF_TL(3) AADFF_TL(5) AADFF_TL(7) AADFF_TL(9) AADFF_TL(11) AADFF_TL(13) }
-#undef AADFF_TL
-#undef AADFF_TLC
-    AADFF_CHECK_LAUNCH();
-    return 0;
 }
 
 }  // extern "C"

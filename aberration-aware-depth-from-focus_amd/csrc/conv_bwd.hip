@@ -1,5 +1,5 @@
-// Backward of the image-space PSF operators for gfx950 (MI355X): the gradients torch.autograd derives for the reference's
-// deeplens/render_psf.py (patch-wise PSF convolution :12-73, per-pixel PSF gather :76-107), as closed forms in plain fp32.
+// Backward of the patch-wise PSF convolution for gfx950 (MI355X): the gradients torch.autograd derives for the reference's
+// deeplens/render_psf.py:12-73, as closed forms in plain fp32 (the per-pixel gather's backward: gather.hip).
 // See include/aadff.h for the entry points and DESIGN.md 4.7 for the design and the measurements.
 //
 // Every sum has a fixed order (no float atomics): results are bitwise reproducible from run to run.  Sums across workgroups
@@ -231,72 +231,6 @@ __global__ __launch_bounds__(256) void map_dpsf_sum_kernel(const float* __restri
     dpsf[idx] = sum;
 }
 
-// ------------------------------------------------------------------------------------
-// (b1) d_psf of the per-pixel gather: d_psf[b][y][x][a][e] = sum_c dy[b][c][y][x] * img[b][c][clamp(y + a - p)][clamp(x + e - p)].
-// C FMAs per output, bound by the B H W ks^2 floats it writes: a workgroup writes the contiguous run of 64 pixels' PSF gradients,
-// consecutive threads consecutive floats; the image window comes through the caches (every pixel is read ks^2 times).
-// ------------------------------------------------------------------------------------
-template <int KS>
-__global__ __launch_bounds__(256) void local_dpsf_kernel(const float* __restrict__ img, const float* __restrict__ dy, float* __restrict__ dpsf,
-                                                         int C, int H, int W, int ks_rt) {
-    const int ks = KS > 0 ? KS : ks_rt, kk = ks * ks, p = ks / 2;
-    const int x0 = blockIdx.x * 64, y = blockIdx.y, b = blockIdx.z;
-    const int npx = min(64, W - x0);
-    float* out = dpsf + (((size_t)b * H + y) * W + x0) * kk;
-    const size_t hw = (size_t)H * W;
-    const float* ib = img + (size_t)b * C * hw;
-    const float* db = dy + (size_t)b * C * hw + (size_t)y * W + x0;
-    for (int idx = threadIdx.x; idx < npx * kk; idx += 256) {
-        const int px = idx / kk, t = idx - px * kk;
-        const int a = t / ks, e = t - a * ks;
-        const int yy = min(max(y + a - p, 0), H - 1), xx = min(max(x0 + px + e - p, 0), W - 1);
-        const float* ip = ib + (size_t)yy * W + xx;
-        float acc = 0.f;
-        for (int cc = 0; cc < C; ++cc) acc = fmaf(db[cc * hw + px], ip[cc * hw], acc);
-        out[idx] = acc;
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// (b2) d_img of the per-pixel gather: every (pixel (y, x), tap (a, e)) whose replicate-clamped source is (Y, X) contributes
-// dy[b][c][y][x] * psf[b][y][x][a][e].  Inside the image that is one tap per source pixel of the ks x ks window (a = Y - y + p);
-// on the first / last row the taps that clamp onto it (a <= p - y, a >= H - 1 - y + p), the same in x.  One thread per (b, Y, X), the
-// PSF value read once for up to 4 channels.  Sums: one partial per source row, added to the pixel's accumulator.
-// ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void local_dimg_kernel(const float* __restrict__ psf, const float* __restrict__ dy, float* __restrict__ dimg,
-                                                        int C, int H, int W, int ks) {
-    const int kk = ks * ks, p = ks / 2;
-    const int X = blockIdx.x * 64 + threadIdx.x, Y = blockIdx.y, b = blockIdx.z;
-    if (X >= W) return;
-    const size_t hw = (size_t)H * W;
-    const int y_lo = max(Y - p, 0), y_hi = min(Y + p, H - 1), x_lo = max(X - p, 0), x_hi = min(X + p, W - 1);
-    for (int c0 = 0; c0 < C; c0 += 4) {
-        const int nc = min(4, C - c0);
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int y = y_lo; y <= y_hi; ++y) {
-            const int a_lo = Y == 0 ? 0 : Y - y + p, a_hi = Y == H - 1 ? ks - 1 : Y - y + p;
-            float part[4] = {0.f, 0.f, 0.f, 0.f};
-            for (int x = x_lo; x <= x_hi; ++x) {
-                const int e_lo = X == 0 ? 0 : X - x + p, e_hi = X == W - 1 ? ks - 1 : X - x + p;
-                const float* dp = dy + ((size_t)b * C + c0) * hw + (size_t)y * W + x;
-                float dv[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) dv[j] = j < nc ? dp[j * hw] : 0.f;
-                const float* pp = psf + (((size_t)b * H + y) * W + x) * kk;
-                for (int a = a_lo; a <= a_hi; ++a)
-                    for (int e = e_lo; e <= e_hi; ++e) {
-                        const float w = pp[a * ks + e];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) part[j] = fmaf(dv[j], w, part[j]);
-                    }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] += part[j];
-        }
-        for (int j = 0; j < nc; ++j) dimg[((size_t)b * C + c0 + j) * hw + (size_t)Y * W + X] = acc[j];
-    }
-}
-
 struct BwdPlan { PatchBounds pb; int ntx, nty; size_t ws_bytes; };
 
 static void plan_map_bwd(BwdPlan& pl, int B, int C, int S, int H, int W, int grid, int ks) {
@@ -360,25 +294,6 @@ int aadff_render_psf_map_stack_bwd(const float* img, const float* psf_maps, cons
         const size_t n = (size_t)S * C * grid * ks * grid * ks;
         hipLaunchKernelGGL(map_dpsf_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, d_psf_or_null, B, C, S, grid, ks, pl.ntx,
                            pl.nty, pl.pb);
-        AADFF_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
-int aadff_local_psf_render_bwd(const float* img, const float* psf, const float* dy, float* d_img_or_null, float* d_psf_or_null, int B, int C,
-                               int H, int W, int ks, aadff_stream_t stream) {
-    AADFF_CHECK_ARG(img && psf && dy, "local_psf_render_bwd: NULL pointer (img, psf, dy)");
-    AADFF_CHECK_ARG(d_img_or_null || d_psf_or_null, "local_psf_render_bwd: d_img and d_psf are both NULL");
-    if (int rc = local_check_shape(B, C, H, W, ks)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 g((W + 63) / 64, H, B);
-    if (d_img_or_null) {
-        hipLaunchKernelGGL(local_dimg_kernel, g, dim3(64), 0, st, psf, dy, d_img_or_null, C, H, W, ks);
-        AADFF_CHECK_LAUNCH();
-    }
-    if (d_psf_or_null) {
-        if (ks == 11) hipLaunchKernelGGL(local_dpsf_kernel<11>, g, dim3(256), 0, st, img, dy, d_psf_or_null, C, H, W, ks);
-        else hipLaunchKernelGGL(local_dpsf_kernel<0>, g, dim3(256), 0, st, img, dy, d_psf_or_null, C, H, W, ks);
         AADFF_CHECK_LAUNCH();
     }
     return 0;

@@ -38,31 +38,19 @@
 #include <cmath>
 #include <type_traits>
 #include "common.h"
+#include "gather_window.h"
+#include "psfnet_common.h"
 
 namespace aadff {
 namespace pnb {
 
-constexpr int NWV = 8, NTH = 64 * NWV;
-constexpr int AP = 256;                 // activation row pitch in halves (psfnet.hip)
+using namespace pn;                     // workgroup shape, activation layout and operand split of the forward (psfnet_common.h)
+
 constexpr int TP = 64;                  // rows per workgroup
 constexpr int NPT = TP / 16;            // pixel tiles
 constexpr int PP = 132;                 // floats per row of the fp32 sigmoid outputs
 constexpr int PLANE = TP * AP;
-constexpr int MAXL = AADFF_PSFNET_MAX_LAYERS;
 constexpr int MAXKS = 11;               // n_out <= 128
-
-typedef _Float16 half8v __attribute__((ext_vector_type(8)));
-typedef _Float16 half4v __attribute__((ext_vector_type(4)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef unsigned uint4v __attribute__((ext_vector_type(4)));
-
-struct Coord {
-    const float* depth;     // [N][H][W] mm (< 0)
-    const float* xs;        // [W]
-    const float* ys;        // [H]
-    const float* foc_z;     // [N][S]
-    float d_min, inv_range;
-};
 
 struct Layers {
     int n;
@@ -70,22 +58,6 @@ struct Layers {
     int tkpad[MAXL], tnpad[MAXL], twoff[MAXL];                 // transposed pack: K = out_features (pad 32), N = in_features (pad 16)
     int texp;                                                  // sum of the transposed pack's per-layer power-of-two exponents
 };
-
-__device__ __forceinline__ int swz(int px, int f) { return px * AP + ((((f >> 3) ^ px) & 15) << 3 | (f & ~127) | (f & 7)); }
-
-// x = hi + lo, hi = fp16(x), lo = fp16(x - hi): the instruction sequence of psfnet.hip (same roundings)
-__device__ __forceinline__ void split4(float4v v, half4v& h, half4v& l) {
-    typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-    const half2v h01 = {(_Float16)v[0], (_Float16)v[1]}, h23 = {(_Float16)v[2], (_Float16)v[3]};
-    unsigned l01, l23;
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\tv_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-        : "=&v"(l01) : "v"(__builtin_bit_cast(unsigned, h01)), "v"(v[0]), "v"(v[1]));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\tv_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-        : "=&v"(l23) : "v"(__builtin_bit_cast(unsigned, h23)), "v"(v[2]), "v"(v[3]));
-    const half2v q01 = __builtin_bit_cast(half2v, l01), q23 = __builtin_bit_cast(half2v, l23);
-    h = (half4v){h01[0], h01[1], h23[0], h23[1]};
-    l = (half4v){q01[0], q01[1], q23[0], q23[1]};
-}
 
 // out^T[feat][px] (+)= sum_k A[feat][k] B[px][k] for this wave's NTL feature tiles (wave, wave + 8) and all TP pixels: the k-loop of
 // psfnet_fused_kernel (weights streamed two k-steps ahead, products hi*hi, hi*lo, lo*hi in that order).
@@ -489,43 +461,13 @@ __global__ __launch_bounds__(256) void psfnet_rows_kernel(Coord coord, long n, l
     *reinterpret_cast<float4v*>(rows + (size_t)rem * 4) = (float4v){coord.xs[xx], coord.ys[yy], z, coord.foc_z[ns]};
 }
 
-// Adjoint of the per-pixel gather for one (n, slice) (local_dimg_kernel of conv_bwd.hip with the stack's dy strides), added to d_img
+// Adjoint of the per-pixel gather for one (n, slice): gather_adjoint (gather_window.h) with the stack's dy strides, added to d_img
 // when `accumulate`: the slices are launched in slice order on one stream, so the sum over the slices has a fixed order.
 __global__ __launch_bounds__(64) void psfnet_dimg_kernel(const float* __restrict__ psf, const float* __restrict__ dy, size_t dy_cstride,
                                                          float* __restrict__ dimg, int C, int H, int W, int ks, int accumulate) {
-    const int kk = ks * ks, p = ks / 2;
-    const int X = blockIdx.x * 64 + threadIdx.x, Y = blockIdx.y;
-    if (X >= W) return;
     const size_t hw = (size_t)H * W;
-    const int y_lo = max(Y - p, 0), y_hi = min(Y + p, H - 1), x_lo = max(X - p, 0), x_hi = min(X + p, W - 1);
-    for (int c0 = 0; c0 < C; c0 += 4) {
-        const int nc = min(4, C - c0);
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int y = y_lo; y <= y_hi; ++y) {
-            const int a_lo = Y == 0 ? 0 : Y - y + p, a_hi = Y == H - 1 ? ks - 1 : Y - y + p;
-            float part[4] = {0.f, 0.f, 0.f, 0.f};
-            for (int x = x_lo; x <= x_hi; ++x) {
-                const int e_lo = X == 0 ? 0 : X - x + p, e_hi = X == W - 1 ? ks - 1 : X - x + p;
-                const float* dp = dy + (size_t)c0 * dy_cstride + (size_t)y * W + x;
-                float dv[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) dv[j] = j < nc ? dp[j * dy_cstride] : 0.f;
-                const float* pp = psf + ((size_t)y * W + x) * kk;
-                for (int a = a_lo; a <= a_hi; ++a)
-                    for (int e = e_lo; e <= e_hi; ++e) {
-                        const float w = pp[a * ks + e];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) part[j] = fmaf(dv[j], w, part[j]);
-                    }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] += part[j];
-        }
-        for (int j = 0; j < nc; ++j) {
-            float* o = dimg + (c0 + j) * hw + (size_t)Y * W + X;
-            *o = accumulate ? *o + acc[j] : acc[j];
-        }
-    }
+    if (accumulate) gather_adjoint<true>(psf, dy, dy_cstride, dimg, hw, C, H, W, ks);
+    else gather_adjoint<false>(psf, dy, dy_cstride, dimg, hw, C, H, W, ks);
 }
 
 struct Plan { int tiles; size_t off_part, off_rows, off_psf, bytes; };       // offsets in floats

@@ -2,7 +2,7 @@
 
 Reference: deeplens/psfnet.py — PSFNet(Lensgroup) :14, render :393-441, pred :375-390,
 depth2z :447-450, get_training_data :135-170, train_psfnet :79-132, ThinLens :489-570.
-The per-pixel PSF application runs in csrc/conv.hip (local_psf_render); ray-traced
+The per-pixel PSF application runs in csrc/gather.hip (local_psf_render); ray-traced
 training targets come from the fused PSF kernel of csrc/trace.hip.
 """
 import math

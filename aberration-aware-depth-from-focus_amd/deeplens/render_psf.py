@@ -1,4 +1,4 @@
-"""Image-space PSF application on MI355X (HIP kernels in csrc/conv.hip).
+"""Image-space PSF application on MI355X (HIP kernels in csrc/conv.hip and csrc/gather.hip).
 
 Each function validates like the reference, then calls its torch custom op (torch.ops.aadff.*, aadff/ops.py), which
 packs pointers for the C ABI.  Same four functions, argument order and assertion messages as the reference's

@@ -1,5 +1,5 @@
 """Shared by tests/test_local_gather_host.py and tests/test_gpu_local_gather.py (not a test module): the cases, inputs, comparators and
-budgets of the forward tests of the per-pixel PSF gather (aadff_local_psf_render, csrc/conv.hip) and of the thin-lens kernel.
+budgets of the forward tests of the per-pixel PSF gather (aadff_local_psf_render, csrc/gather.hip) and of the thin-lens kernel.
 
 Comparator: oracle.conv.local_psf_render (the reference's unfold form) in float64.
 
@@ -61,7 +61,7 @@ def case_id(case, signed=False):
 
 
 def generic_lds_bytes(case):
-    """Dynamic LDS request of the generic kernel (csrc/conv.hip, aadff_local_psf_render)."""
+    """Dynamic LDS request of the generic kernel (csrc/gather.hip, aadff_local_psf_render)."""
     B, C, H, W, ks = case
     npx = 64 if ks <= 15 else 16
     return 4 * (npx * ks * ks + C * ks * (npx + ks - 1))
@@ -169,8 +169,8 @@ THIN_CASES = list(tc.CASES) + [_thin_case(ks, C, H, W) for ks, C, H, W in ((3, 2
 
 
 def thin_sequential32(case, img, depth, fds):
-    """float32 [N,C,S,H,W]: the thin-lens render as thinlens_kernel orders it.  The coc chain in float32 in the reference's operation
-    order through rad^2, weights exp(-du^2/2/rad^2) * exp(-dv^2/2/rad^2) with float32 torch.exp cut at du^2 + dv^2 < rad^2, the weight
+    """float32 [N,C,S,H,W]: the thin-lens render as render_slice (csrc/thinlens.hip) orders it.  The coc chain in float32 in the reference's
+    operation order through rad^2, weights exp(-du^2/2/rad^2) * exp(-dv^2/2/rad^2) with float32 torch.exp cut at du^2 + dv^2 < rad^2, the weight
     sum and the channel sums sequential in tap order, out = acc * (1 / wsum)."""
     foc_len, fnum, ks, ssize, sres = tc.lens_args(case)
     f32 = np.float32

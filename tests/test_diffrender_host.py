@@ -1,4 +1,4 @@
-"""CPU: the backward entry points of the image-space operators (csrc/conv_bwd.hip) validate their arguments before any HIP
+"""CPU: the backward entry points of the image-space operators (csrc/conv_bwd.hip, csrc/gather.hip) validate their arguments before any HIP
 call, the workspace query is host arithmetic, and aadff.diffrender imports without a GPU."""
 import ctypes as C
 

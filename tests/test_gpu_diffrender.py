@@ -1,5 +1,5 @@
 """GPU tests (run with `-m gpu` on an MI355X) of aadff.diffrender: gradients of the image-space PSF operators from the HIP
-kernels of csrc/conv_bwd.hip against torch.autograd through oracle/conv.py evaluated in float64 on the CPU.
+kernels of csrc/conv_bwd.hip and csrc/gather.hip against torch.autograd through oracle/conv.py evaluated in float64 on the CPU.
 
 Tolerance of every gradient: 4 x d32, where d32 is the relative-L2 distance of the oracle's OWN float32 autograd from its
 float64 autograd on the same inputs, computed here; the factor 4 allows for a different summation order of the same fp32

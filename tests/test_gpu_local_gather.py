@@ -1,5 +1,5 @@
 """GPU tests (run with `-m gpu` on an MI355X): the forward values of the per-pixel PSF gather (aadff_local_psf_render: the LDS-DMA, the
-direct and the generic kernels of csrc/conv.hip) and of thinlens_kernel against float64 on the CPU.  The gather is the yardstick of the
+direct and the generic kernels of csrc/gather.hip) and of the thin-lens forward (csrc/thinlens.hip) against float64 on the CPU.  The gather is the yardstick of the
 thin-lens and the fused PSF-network gather tests of tests/test_gpu_parity.py; here it is anchored itself.
 
 tests/local_gather_common.py has the cases, the comparator (oracle.conv.local_psf_render in float64), the float32 restatement in the
@@ -142,8 +142,8 @@ def _lens(case):
 
 @pytest.mark.parametrize("case", lg.THIN_CASES, ids=[c[0] for c in lg.THIN_CASES])
 def test_thinlens_forward_against_float64(case, margin):
-    """thinlens_kernel, slice by slice, against the float64 oracle on every pixel that tc.keep_rows keeps (next to a jump of the cut or
-    a kink a last-bit difference moves a whole ring of taps; nothing else is excluded): rel_l2 <= 4 x d32seq of thin_sequential32 on
+    """thinlens_kernel (csrc/thinlens.hip), slice by slice, against the float64 oracle on every pixel that tc.keep_rows keeps (next to a jump of the
+    cut or a kink a last-bit difference moves a whole ring of taps; nothing else is excluded): rel_l2 <= 4 x d32seq of thin_sequential32 on
     the same pixels."""
     img, depth, fds, keep, share, out64, seq, d32seq = lg.thin_reference(case)
     assert share <= tc.MAX_MASKED

@@ -1,5 +1,5 @@
 """GPU tests (run with `-m gpu` on an MI355X) of aadff.diffrender.thinlens_render / thinlens_render_stack and ThinLens.render_stack:
-the stack-fused forward and the fused backward of the thin-lens baseline (csrc/thinlens_bwd.hip) against torch.autograd through the
+the stack-fused forward and the fused backward of the thin-lens baseline (csrc/thinlens.hip) against torch.autograd through the
 oracle evaluated in float64 on the CPU (tests/thinlens_grad_common.py has the comparator, the cases and the cotangent mask).
 
 Budget of every gradient (relative L2, masked cotangent): 4 x r x d32, as for the PSF-network renderer.
@@ -94,6 +94,25 @@ def test_render_stack_is_bit_equal_to_the_slice_loop(case):
     got = lens.render_stack(x, d, f)
     assert got.shape == want.shape == (case[1], case[2], case[3], case[4], case[5]) and torch.equal(got, want)
     assert torch.equal(lens.render_stack(img, depth, fds), want.cpu())                   # inputs on the CPU: result on the CPU
+
+
+@pytest.mark.parametrize("sign", (+1, -1), ids=("positive_depth", "negative_depth"))
+@pytest.mark.parametrize("B,C,H,W,ks", ((2, 3, 5, 70, 11),            # every row clamped, a ragged second run
+                                        (1, 4, 9, 64, 3),             # the run-time channel path, exactly one run
+                                        (1, 1, 13, 130, 13)))         # the largest compiled ks, three runs
+def test_single_focus_op_is_the_stack_op_with_one_slice(B, C, H, W, ks, sign):
+    """The single-focus kernel and the stack kernel call one device body (render_slice, csrc/thinlens.hip): foc_dist [B] is foc_dists
+    [B,1] and [B,C,H,W] the memory of [B,C,1,H,W].  Both depth conventions, so the kernels' `negate` word is 0 once and 1 once."""
+    case = (f"{B}x{C}x{H}x{W}_S1_ks{ks}", B, C, 1, H, W, ks, (256, 256), 2.8, [(700.0 + 500.0 * n,) for n in range(B)], sign, (500.0, 5000.0))
+    img, depth, fds, _ = tc.case_inputs(case)
+    assert bool((depth < 0).any()) == (sign < 0)
+    lens = _lens(case)
+    x, d, f = img.to(DEV), depth.to(DEV), fds.to(DEV)
+    consts = (ks, tc.FOC_LEN, 2.8, lens.ps, float(lens.d_min), float(lens.d_max))
+    one = torch.ops.aadff.thinlens_render(x, d, f[:, 0].contiguous(), *consts)
+    stack = torch.ops.aadff.thinlens_render_stack(x, d, f, *consts)
+    assert one.shape == (B, C, H, W) and stack.shape == (B, C, 1, H, W)
+    assert torch.equal(one, stack[:, :, 0]) and torch.isfinite(one).all() and not torch.equal(one, x)
 
 
 def test_other_kernel_sizes_and_channels(margin):

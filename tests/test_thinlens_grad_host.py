@@ -1,4 +1,4 @@
-"""CPU: the host side of the differentiable thin-lens renderer (csrc/thinlens_bwd.hip, aadff/ops.py, aadff/diffrender.py): exported
+"""CPU: the host side of the differentiable thin-lens renderer (csrc/thinlens.hip, aadff/ops.py, aadff/diffrender.py): exported
 symbols, argument errors of the new C entries without a GPU, fake-tensor shapes of the new ops, the workspace formula, the conditions on
 every GPU test case (excluded share, the oracle's own float32 distance), and the closed forms of DESIGN.md 4.9 restated in float64
 torch against the oracle's float64 autograd (tests/thinlens_grad_common.py)."""

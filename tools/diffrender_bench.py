@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Forward + backward of the differentiable image-space operators (aadff.diffrender, csrc/conv_bwd.hip) against the reference's
+"""Forward + backward of the differentiable image-space operators (aadff.diffrender, csrc/conv_bwd.hip and csrc/gather.hip) against the reference's
 formulation on the same GPU: oracle.conv.render_psf_map / local_psf_render (F.pad + F.conv2d per patch, unfold / fold) on
 device tensors with torch.autograd.  Same inputs, warmed up, the two legs alternating, HIP events around >= --seconds of work
 per leg and repeat.  Shapes: 1x3x1024^2 grid 11 ks 11 single slice, the same as a 10-slice stack (oracle: the slice loop),

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Forward + backward of the differentiable thin-lens renderer (aadff.diffrender.thinlens_render_stack, csrc/thinlens_bwd.hip) against
+"""Forward + backward of the differentiable thin-lens renderer (aadff.diffrender.thinlens_render_stack, csrc/thinlens.hip) against
 the reference's tensor form under torch autograd on the same GPU (lens.coc -> [N,H,W,ks,ks] Gaussian PSFs -> the HIP gather with its
 HIP backward, aadff.diffrender._thinlens_tensor_form), at 2x3x480x640 x 8 slices and at 1x3x1024^2 x 10, ks 11.  Gradients to the
 image, the depth map and the focus distances in both legs.  The tensor leg runs one slice at a time (forward + backward per slice,
