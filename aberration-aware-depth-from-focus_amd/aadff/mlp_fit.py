@@ -69,7 +69,9 @@ class FusedFit:
                     p.data = self.flat[off:off + k].view_as(p)
                     lst.append(off)
                     off += k
-        self.chain = os.environ.get("AADFF_FIT_CHAIN", "1") != "0" and self.L <= _abi.FIT_MAX_LAYERS and all(k % 4 == 0 for k in self.K)
+        # the chain kernel takes 2..AADFF_FIT_MAX_LAYERS layers (its prefetch runs two passes ahead); a single Linear + Sigmoid and
+        # deeper networks run in the layer-by-layer form
+        self.chain = os.environ.get("AADFF_FIT_CHAIN", "1") != "0" and 2 <= self.L <= _abi.FIT_MAX_LAYERS and all(k % 4 == 0 for k in self.K)
         # ---- bf16 operand copies [W | W^T | bias] per layer and the maps flat index -> slot.  Layer-by-layer form: row-major
         # with padded leading dimensions.  Chain form: MFMA FRAGMENT ORDER - a matrix M [rows][cols] is stored as
         # [tile = row // 16][k-step = col // 32][lane = ((col % 32) // 8) * 16 + row % 16][col % 8], zero padded to whole tiles and

@@ -1242,8 +1242,12 @@ def test_fit_kernels_gradients_match_torch(bs, ks, hidden, layers, chain, monkey
     from deeplens.psfnet_arch import MLP
     torch.manual_seed(bs + ks)
     net = MLP(4, ks * ks, hidden, layers).to(DEV)
-    ref = copy.deepcopy(net)
     rng = np.random.Generator(np.random.PCG64(bs))
+    with torch.no_grad():                                        # initialize_weights zeroes every bias: +- 0.1, as mlp_state_dict draws them
+        for m in net.net:
+            if isinstance(m, torch.nn.Linear):
+                m.bias.copy_(tt((rng.random(m.out_features, dtype=np.float32) * 2 - 1) * 0.1))
+    ref = copy.deepcopy(net)
     inp = tt(rng.random((bs, 4), dtype=np.float32) * 2 - 1).to(DEV)
     psf = tt(rng.random((bs, ks * ks), dtype=np.float32)).to(DEV)
     psf /= psf.sum(-1, keepdim=True)
