@@ -1583,6 +1583,105 @@ __global__ __launch_bounds__(kSpotThreads) void spot_moments_kernel(const float*
     if (nan_flag && flags) atomicOr(flags, 1);    // found nan in ft in non-diff newton method (surfaces.py:555-558)
 }
 
+// ------------------------------------------------------------------------------------
+// Ray-traced image rendering: sensor pixel -> exit pupil -> backwards through the lens -> object plane ->
+// bilinear sample of the scene.  One lane owns one (pixel, channel): it loops over the spp samples and keeps the valid
+// count and the running sums of up to kRenderMaxB images in registers (the rays do not depend on the image), so there is
+// no atomic and no cross-lane reduction, every output is written once and a launch is bit-reproducible.  A wave covers an
+// 8 x 8 pixel block, a workgroup 16 x 16, blockIdx.z is the channel (= wavelength: the surface table stays wave-uniform);
+// neighbouring lanes land on neighbouring texels, which ordinary global loads then fetch from the same cache lines.
+// ------------------------------------------------------------------------------------
+constexpr int kRenderTile = 16, kRenderMaxB = 4, kRenderAngles = 8;
+
+// Jitter uniform number `idx` of a render with `seed`: output idx of the SplitMix64 sequence seeded with `seed` (Steele, Lea,
+// Flood 2014), top 24 bits -> [0, 1).  idx is the flat index into u[3, spp, 2, H, W]: ((channel * spp + sample) * 2 + which) * H * W
+// + pixel, so the value is a pure function of (seed, channel, sample, which, pixel) and aadff_sensor_uniforms reproduces it.
+__device__ __forceinline__ float sensor_uniform(unsigned long long seed, unsigned long long idx) {
+    unsigned long long z = seed + (idx + 1ull) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (float)(unsigned)(z >> 40) * 5.9604644775390625e-8f;          // 24 bits * 2^-24
+}
+
+__global__ __launch_bounds__(256) void sensor_uniforms_kernel(unsigned long long seed, size_t n, float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = sensor_uniform(seed, i);
+}
+
+struct RenderGeom {
+    int H, W, spp, rings;                 // rings = spp / 8
+    float pupil_z, r2_step;               // r2_step = pupil_r^2 / spp * 8 (sample_pupil, optics.py:579)
+    float x0, y0, ps;                     // sensor point of pixel (i, j): (x0 + (j+1) ps, y0 - (i+1) ps), x0 = -Ws/2, y0 = Hs/2
+    float depth, inv_texel, cu, cv;       // uj = cu - px inv_texel, vi = cv + py inv_texel; inv_texel = 1 / (scale ps), cu = W/2 - 1, cv = H/2 - 1
+};
+
+template <int NB>
+__global__ __launch_bounds__(kRenderTile * kRenderTile) void render_raytraced_kernel(
+    const float* __restrict__ img, const float* __restrict__ u, unsigned long long seed, const aadff_surface_t* __restrict__ surf, int n_surf,
+    RenderGeom g, int vignetting, const aadff_lens_state_t* __restrict__ state, float* __restrict__ out, float* __restrict__ count,
+    unsigned char* __restrict__ valid_out, int* flags) {
+    const float d_sensor = fresh_uniform(&state->d_sensor);
+    const int c = blockIdx.z, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = blockIdx.x * kRenderTile + (wave & 1) * 8 + (lane & 7);
+    const int i = blockIdx.y * kRenderTile + (wave >> 1) * 8 + (lane >> 3);
+    if (i >= g.H || j >= g.W) return;
+    const size_t HW = (size_t)g.H * g.W, pix = (size_t)i * g.W + j;
+    const aadff_surface_t* tab = surf + (size_t)c * n_surf;
+    const float* im = img + (size_t)c * HW;                               // image b: im + b * 3 * HW
+    const float sx = g.x0 + (float)(j + 1) * g.ps, sy = g.y0 - (float)(i + 1) * g.ps;
+    const float fW = (float)g.W, fH = (float)g.H;
+    float acc[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc[b] = 0.f;
+    float cnt = 0.f;
+    int nan_flag = 0, sec = 0, ring = 0;
+#pragma unroll 1
+    for (int s = 0; s < g.spp; ++s) {
+        // sample s = sector * rings + ring (optics.py:574-582); theta draw, then r^2 draw
+        const size_t k = (size_t)(c * g.spp + s) * 2 * HW + pix;
+        float ut, ur;
+        if (u) { ut = u[k]; ur = u[k + HW]; }
+        else { ut = sensor_uniform(seed, k); ur = sensor_uniform(seed, k + HW); }
+        const float rev = (ut + (float)sec) * (1.f / kRenderAngles);      // theta / (2 pi)
+        const float rr = fsqrt((ur + (float)ring) * g.r2_step);
+        Ray r = ray_to(sx, sy, d_sensor, rr * __builtin_amdgcn_cosf(rev), rr * __builtin_amdgcn_sinf(rev), g.pupil_z);
+        trace_range<false>(tab, 0, n_surf, false, r, nan_flag);
+        propagate_to(r, g.depth);
+        const float uj = g.cu - r.ox * g.inv_texel, vi = g.cv + r.oy * g.inv_texel;
+        // NaN-safe: a dead ray's coordinates are never turned into an index
+        const bool ok = (r.ra > 0.f) && (uj >= -1.f) && (uj <= fW) && (vi >= -1.f) && (vi <= fH);
+        if (valid_out) valid_out[(size_t)(c * g.spp + s) * HW + pix] = ok ? 1 : 0;
+        if (ok) {
+            const float fu = floorf(uj), fv = floorf(vi);
+            const float ax = uj - fu, ay = vi - fv;
+            const int xi = (int)fu, yi = (int)fv;
+            const int xa = min(max(xi, 0), g.W - 1), xb = min(max(xi + 1, 0), g.W - 1);       // replicate border
+            const size_t ra = (size_t)min(max(yi, 0), g.H - 1) * g.W, rb = (size_t)min(max(yi + 1, 0), g.H - 1) * g.W;
+            cnt += 1.f;
+            // every fusion is written out and none is left to the compiler, which contracts differently from one instantiation
+            // to the next: an image must render to the same bits whichever launch of a chunked batch it falls into
+            {
+#pragma clang fp contract(off)
+                const float bx = 1.f - ax, by = 1.f - ay;
+#pragma unroll
+                for (int b = 0; b < NB; ++b) {
+                    const float* p = im + (size_t)b * 3 * HW;
+                    const float top = __builtin_fmaf(ax, p[ra + xb], bx * p[ra + xa]);
+                    const float bot = __builtin_fmaf(ax, p[rb + xb], bx * p[rb + xa]);
+                    acc[b] += __builtin_fmaf(ay, bot, by * top);
+                }
+            }
+        }
+        if (++ring == g.rings) { ring = 0; ++sec; }
+    }
+    const float den = vignetting ? (float)g.spp : cnt;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) out[((size_t)b * 3 + c) * HW + pix] = cnt > 0.f ? acc[b] / den : 0.f;
+    if (count) count[(size_t)c * HW + pix] = cnt;
+    if (nan_flag && flags) atomicOr(flags, 1);    // found nan in ft in non-diff newton method (surfaces.py:555-558)
+}
+
 }  // namespace aadff
 
 using namespace aadff;
@@ -1846,6 +1945,68 @@ int aadff_spot_moments(const float* points, int P, const float* u, int spp, int 
     hipLaunchKernelGGL(spot_moments_kernel, dim3(P), dim3(kSpotThreads), 0, (hipStream_t)stream, points, P, u, spp, num_angle, n_pass,
                        surf, n_surf, pupil_z, r2_step, state, ref_mode, want_s2, reinterpret_cast<float4*>(moments), flags_or_null);
     AADFF_CHECK_LAUNCH();
+    return 0;
+}
+
+int aadff_sensor_uniforms(unsigned long long seed, int spp, int H, int W, float* out, aadff_stream_t stream) {
+    AADFF_CHECK_ARG(out, "sensor_uniforms: NULL pointer");
+    AADFF_CHECK_ARG(spp > 0 && spp % kRenderAngles == 0, "sensor_uniforms: spp=%d must be a positive multiple of %d", spp, kRenderAngles);
+    AADFF_CHECK_ARG(H >= 1 && W >= 1, "sensor_uniforms: bad sizes H=%d W=%d", H, W);
+    const size_t n = (size_t)3 * spp * 2 * H * W;
+    AADFF_CHECK_ARG((n + 255) / 256 <= 0x7fffffffull, "sensor_uniforms: 3*spp*2*H*W = %zu is too large for one launch", n);
+    hipLaunchKernelGGL(sensor_uniforms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed, n, out);
+    AADFF_CHECK_LAUNCH();
+    return 0;
+}
+
+int aadff_render_raytraced(const float* img, int B, int H, int W, const float* u_or_null, unsigned long long seed, int spp,
+                           const aadff_surface_t* surf_rgb, int n_surf, float pupil_z, float pupil_r, float sensor_w, float sensor_h,
+                           float pixel_size, float depth, float scale, int vignetting, const aadff_lens_state_t* state, float* out,
+                           float* count_or_null, unsigned char* valid_or_null, int* flags_or_null, aadff_stream_t stream) {
+    AADFF_CHECK_ARG(img && surf_rgb && state && out, "render_raytraced: NULL pointer");
+    AADFF_CHECK_ARG(B >= 1 && H >= 1 && W >= 1, "render_raytraced: bad sizes B=%d H=%d W=%d", B, H, W);
+    AADFF_CHECK_ARG(spp > 0 && spp % kRenderAngles == 0, "render_raytraced: spp=%d must be a positive multiple of %d (stratified pupil samples)",
+                    spp, kRenderAngles);
+    AADFF_CHECK_ARG(n_surf > 0 && n_surf <= AADFF_MAX_SURF, "render_raytraced: n_surf %d outside [1,%d]", n_surf, AADFF_MAX_SURF);
+    AADFF_CHECK_ARG(std::isfinite(pupil_z) && std::isfinite(pupil_r) && pupil_r >= 0.f, "render_raytraced: bad pupil (z=%g, r=%g)",
+                    (double)pupil_z, (double)pupil_r);
+    AADFF_CHECK_ARG(std::isfinite(sensor_w) && std::isfinite(sensor_h) && sensor_w > 0.f && sensor_h > 0.f,
+                    "render_raytraced: bad sensor size (%g x %g mm)", (double)sensor_w, (double)sensor_h);
+    const double texel = (double)scale * (double)pixel_size;
+    AADFF_CHECK_ARG(std::isfinite(texel) && texel > 0.0 && pixel_size > 0.f,
+                    "render_raytraced: scale * pixel_size must be positive (scale=%g, pixel_size=%g)", (double)scale, (double)pixel_size);
+    AADFF_CHECK_ARG(depth < 0.f && std::isfinite(depth), "render_raytraced: depth %g must be negative (object plane in front of the lens)",
+                    (double)depth);
+    const unsigned gx = (W + kRenderTile - 1) / kRenderTile, gy = (H + kRenderTile - 1) / kRenderTile;
+    AADFF_CHECK_ARG(gy <= 65535u, "render_raytraced: H=%d exceeds %d rows", H, 65535 * kRenderTile);
+    RenderGeom g;
+    g.H = H; g.W = W; g.spp = spp; g.rings = spp / kRenderAngles;
+    g.pupil_z = pupil_z;
+    g.r2_step = (float)((double)pupil_r * (double)pupil_r / spp * kRenderAngles);
+    g.x0 = (float)(-(double)sensor_w / 2); g.y0 = (float)((double)sensor_h / 2); g.ps = pixel_size;
+    g.depth = depth; g.inv_texel = (float)(1.0 / texel);
+    g.cu = (float)(W / 2.0 - 1.0); g.cv = (float)(H / 2.0 - 1.0);
+    const size_t plane = (size_t)3 * H * W;
+    // the rays do not depend on the image: every launch traces the same samples for its (up to) kRenderMaxB images
+    for (int b0 = 0; b0 < B; b0 += kRenderMaxB) {
+        const int nb = std::min(kRenderMaxB, B - b0);
+        const float* im = img + (size_t)b0 * plane;
+        float* o = out + (size_t)b0 * plane;
+        float* cnt = b0 == 0 ? count_or_null : nullptr;
+        unsigned char* val = b0 == 0 ? valid_or_null : nullptr;
+        const dim3 grid(gx, gy, 3), block(kRenderTile * kRenderTile);
+#define AADFF_RENDER_LAUNCH(NB)                                                                                                    \
+    hipLaunchKernelGGL(render_raytraced_kernel<NB>, grid, block, 0, (hipStream_t)stream, im, u_or_null, seed, surf_rgb, n_surf, g, \
+                       vignetting, state, o, cnt, val, flags_or_null)
+        switch (nb) {
+            case 1: AADFF_RENDER_LAUNCH(1); break;
+            case 2: AADFF_RENDER_LAUNCH(2); break;
+            case 3: AADFF_RENDER_LAUNCH(3); break;
+            default: AADFF_RENDER_LAUNCH(4); break;
+        }
+#undef AADFF_RENDER_LAUNCH
+        AADFF_CHECK_LAUNCH();
+    }
     return 0;
 }
 

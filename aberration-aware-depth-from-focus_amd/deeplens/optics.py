@@ -646,6 +646,33 @@ class Lensgroup(DeepObj):
         o = torch.stack((x, y, torch.full_like(x, pupilz)), -1)
         return o.to(self._ray_device())
 
+    @torch.no_grad()
+    def sample_sensor(self, spp=64, pupil=True, wvln=DEFAULT_WAVE, sub_pixel=False):
+        """Rays [spp, H, W, 3] from the sensor pixels towards stratified points of the exit pupil (reference:
+        optics.py:494-535): pixel (i, j) is represented by its bottom-right corner, x = linspace(-Ws/2, Ws/2, W+1)[1:],
+        y = linspace(Hs/2, -Hs/2, H+1)[1:], z = d_sensor; the pupil points are `sample_pupil(sensor_res, spp)` on the exit
+        pupil.  The two switches raise as in the reference."""
+        if pupil is not True:
+            raise Exception("This feature has been abandoned.")
+        if sub_pixel:
+            raise Warning("This feature is not finished yet.")
+        dev = self._ray_device()
+        x1, y1 = torch.meshgrid(torch.linspace(-self.sensor_size[1] / 2, self.sensor_size[1] / 2, self.sensor_res[1] + 1, device=dev)[1:],
+                                torch.linspace(self.sensor_size[0] / 2, -self.sensor_size[0] / 2, self.sensor_res[0] + 1, device=dev)[1:],
+                                indexing="xy")
+        z1 = torch.full_like(x1, self.d_sensor)
+        pupilz, pupilr = self.exit_pupil()
+        o2 = self.sample_pupil(self.sensor_res, spp, pupilr=pupilr, pupilz=pupilz)
+        o = torch.broadcast_to(torch.stack((x1, y1, z1), 2), o2.shape)
+        return Ray(o, o2 - o, wvln=wvln, device=dev)
+
+    def render_raytraced(self, img, depth=DEPTH, spp=64, scale=None, u=None, seed=None, vignetting=False, return_aux=False):
+        """img [B,3,H,W] rendered by tracing `spp` rays per pixel and channel from the sensor through the lens to the object
+        plane at `depth`: `aadff.raytrace.render_raytraced` (one fused launch)."""
+        from aadff import raytrace
+        return raytrace.render_raytraced(self, img, depth=depth, spp=spp, scale=scale, u=u, seed=seed, vignetting=vignetting,
+                                         return_aux=return_aux)
+
     def _ray_device(self):
         """where the rays of the analysis live: strict / edge lenses keep them on the host (the reference's arithmetic)"""
         return torch.device("cpu") if self.parity != "fast" else self.device
@@ -1014,7 +1041,8 @@ class Lensgroup(DeepObj):
         which the reference snapshot does not define (AttributeError there) - refused here with the way out named."""
         if method != "psf":
             raise NotImplementedError(f"render_single_img(method='{method}'): only method='psf' exists (the reference's 'raytracing' "
-                                      "branch calls methods its snapshot lacks); pass method='psf'")
+                                      "branch calls methods its snapshot lacks); pass method='psf', or render by ray tracing with "
+                                      "Lensgroup.render_raytraced / aadff.raytrace.render_raytraced")
         if not isinstance(img_org, np.ndarray):
             raise Exception("This function only supports ndarray input. If you want to render an image batch, use `render` function.")
         H, W, Cn = img_org.shape

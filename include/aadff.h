@@ -538,6 +538,29 @@ int aadff_spot_moments(const float* points, int P, const float* u, int spp, int 
                        const aadff_lens_state_t* state, int ref_mode, int want_s2, float* moments,
                        int* flags_or_null, aadff_stream_t stream);
 
+/* Ray-traced image rendering (no counterpart in the reference snapshot, whose 'raytracing' branch of
+ * render_single_img calls methods it does not define).  For every pixel (i, j) of an H x W sensor and every channel c (surf_rgb
+ * [3][n_surf]: the tables of WAVE_RGB), spp rays leave the sensor point (-sensor_w/2 + (j+1) ps, sensor_h/2 - (i+1) ps, d_sensor)
+ * (sample_sensor, deeplens/optics.py:494-535; d_sensor is read from `state` on the device) towards stratified points of the exit
+ * pupil (pupil_z, pupil_r; sample_pupil with 8 sectors: sample s has sector s / (spp/8), ring s % (spp/8), theta = (u[c,s,0,i,j] +
+ * sector) 2 pi / 8, r^2 = (u[c,s,1,i,j] + ring) pupil_r^2 8 / spp), are traced backwards through all surfaces and propagated to
+ * z = depth (< 0), where they land at (px, py).  Scene coordinates uj = W/2 - 1 - px / (scale ps), vi = H/2 - 1 + py / (scale ps); a
+ * ray counts if it survived every surface and -1 <= uj <= W, -1 <= vi <= H; its value is the bilinear sample of img[b, c] at (vi, uj)
+ * (texel centres at integers, indices clamped to the image).  out [B,3,H,W] = sum value / count, 0 where count = 0; with vignetting
+ * != 0 sum value / spp.  count_or_null [3,H,W] the valid rays per pixel (float), valid_or_null [3,spp,H,W] the per-ray validity
+ * (bytes; diagnostics).  u_or_null [3,spp,2,H,W] raw uniforms, or NULL: the kernel then draws uniform number idx (the flat index
+ * into that array) as aadff_sensor_uniforms(seed) defines it.  spp a multiple of 8.  One lane per (pixel, channel), no atomics:
+ * bit-reproducible; B > 4 runs as launches of 4 images over the same rays.  flags bit 0: NaN in a Newton residual. */
+int aadff_render_raytraced(const float* img, int B, int H, int W, const float* u_or_null, unsigned long long seed, int spp,
+                           const aadff_surface_t* surf_rgb, int n_surf, float pupil_z, float pupil_r, float sensor_w, float sensor_h,
+                           float pixel_size, float depth, float scale, int vignetting, const aadff_lens_state_t* state, float* out,
+                           float* count_or_null, unsigned char* valid_or_null, int* flags_or_null, aadff_stream_t stream);
+
+/* The uniforms aadff_render_raytraced draws when it is given none: out [3,spp,2,H,W], element idx = output idx of the SplitMix64
+ * sequence seeded with `seed` (z = seed + (idx+1) 0x9E3779B97F4A7C15; z = (z ^ z>>30) 0xBF58476D1CE4E5B9; z = (z ^ z>>27)
+ * 0x94D049BB133111EB; z ^= z>>31), its top 24 bits times 2^-24: values in [0, 1). */
+int aadff_sensor_uniforms(unsigned long long seed, int spp, int H, int W, float* out, aadff_stream_t stream);
+
 /* Bilinear splat of sensor hits into ks x ks histograms + normalisation.  Replaces
  * forward_integral / assign_points_to_pixels, deeplens/monte_carlo.py:9-121 and the
  * division of deeplens/optics.py:978.  o [spp,N,3], ra [spp,N], centre [N,2];
