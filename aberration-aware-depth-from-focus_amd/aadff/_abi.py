@@ -128,6 +128,8 @@ PROTOTYPES = {
     "aadff_spot_moments": [_P, _I, _P, _I, _I, _I, _P, _I, _F, _F, _P, _I, _I, _P, _P, _P],
     "aadff_render_raytraced": [_P, _I, _I, _I, _P, C.c_ulonglong, _I, _P, _I, _F, _F, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P],
     "aadff_sensor_uniforms": [C.c_ulonglong, _I, _I, _I, _P, _P],
+    "aadff_render_raytraced_layered": [_P, _P, _I, _I, _I, _P, C.c_ulonglong, _I, _P, _I, _F, _F, _F, _F, _F, _I, _P, _P, _I, _P, _P, _P, _P, _P,
+                                       _P, _P],
     "aadff_psf_points": [_P, _I, _I, _I, _P, _P, LensConst, _P, _P, _I, _L, _L, _P, _I, _L, _L, _I, _I, _I, _P, _P, _P, _P],
     "aadff_psf_points_staged": [_P, _I, _I, _I, _P, _P, LensConst, _P, _P, _I, _L, _L, _P, _I, _L, _L, _I, _I, _I, _P, _P, _P,
                                 C.POINTER(Stage), _P],

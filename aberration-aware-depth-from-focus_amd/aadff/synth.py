@@ -43,6 +43,15 @@ def synth_depth_mm(h, w, seed=5678, dmin=500.0, dmax=5000.0, planes=12):
     return np.ascontiguousarray(np.clip(d, dmin, dmax).astype(np.float32))
 
 
+def synth_disc_depth_mm(h, w, near=-600.0, back=(-1500.0, -3000.0), radius=0.25):
+    """Depth map [h,w] float32, NEGATIVE millimetres (in front of the lens): a disc of `radius` x min(h, w) at `near` in the centre
+    over a background that slants from back[0] at the left edge to back[1] at the right one.  Returns (depth, disc mask bool)."""
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    disc = (yy - (h - 1) / 2) ** 2 + (xx - (w - 1) / 2) ** 2 <= (radius * min(h, w)) ** 2
+    d = back[0] + (back[1] - back[0]) * xx / max(w - 1, 1)
+    return np.ascontiguousarray(np.where(disc, near, d).astype(np.float32)), disc
+
+
 MLP_LAYERS = [(4, 64), (64, 256)] + [(256, 256)] * 8 + [(256, 121)]
 
 

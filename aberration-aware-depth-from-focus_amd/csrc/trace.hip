@@ -1682,6 +1682,122 @@ __global__ __launch_bounds__(kRenderTile * kRenderTile) void render_raytraced_ke
     if (nan_flag && flags) atomicOr(flags, 1);    // found nan in ft in non-diff newton method (surfaces.py:555-558)
 }
 
+// ------------------------------------------------------------------------------------
+// Ray-traced rendering of a layered RGB-D scene: the scene is L fronto-parallel planes z_0 > ... > z_{L-1}
+// (nearest first) and a map layer[b] [H,W] that says which plane a texel lies on.  The rays, the lane layout and the sampling
+// are render_raytraced_kernel's; a ray that survived the lens is propagated from its last surface to every plane in turn and
+// composites front to back with a transmittance T (per ray and image: V += T q, A += T a, T *= 1 - a, where a and q are the
+// bilinear forms of the texels' membership in the plane and of their membership-selected values).  Per image the lane keeps
+// the sums of V and A over its rays; no atomics, every output written once.  The plane table is a kernel argument: indexed by
+// the wave-uniform loop counter it is read through scalar loads.  With L = 1 and layer == 0 every step reduces to
+// render_raytraced_kernel's, to the bit (a = 1 exactly, V = q, A = 1).
+// ------------------------------------------------------------------------------------
+struct RenderLayers {
+    int L;
+    float z[AADFF_RENDER_MAX_LAYERS], inv_texel[AADFF_RENDER_MAX_LAYERS];    // inv_texel[l] = 1 / (scale_l ps)
+};
+
+template <int NB>
+__global__ __launch_bounds__(kRenderTile * kRenderTile) void render_raytraced_layered_kernel(
+    const float* __restrict__ img, const unsigned char* __restrict__ layer, const float* __restrict__ u, unsigned long long seed,
+    const aadff_surface_t* __restrict__ surf, int n_surf, RenderGeom g, RenderLayers lt, int vignetting,
+    const aadff_lens_state_t* __restrict__ state, float* __restrict__ out, float* __restrict__ coverage, float* __restrict__ alive_out,
+    unsigned char* __restrict__ alive_rays, int* flags) {
+    const float d_sensor = fresh_uniform(&state->d_sensor);
+    const int c = blockIdx.z, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = blockIdx.x * kRenderTile + (wave & 1) * 8 + (lane & 7);
+    const int i = blockIdx.y * kRenderTile + (wave >> 1) * 8 + (lane >> 3);
+    if (i >= g.H || j >= g.W) return;
+    const size_t HW = (size_t)g.H * g.W, pix = (size_t)i * g.W + j;
+    const aadff_surface_t* tab = surf + (size_t)c * n_surf;
+    const float* im = img + (size_t)c * HW;                               // image b: im + b * 3 * HW, its layer map: layer + b * HW
+    const float sx = g.x0 + (float)(j + 1) * g.ps, sy = g.y0 - (float)(i + 1) * g.ps;
+    const float fW = (float)g.W, fH = (float)g.H;
+    float sumV[NB], sumA[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) { sumV[b] = 0.f; sumA[b] = 0.f; }
+    float cnt = 0.f;
+    int nan_flag = 0, sec = 0, ring = 0;
+#pragma unroll 1
+    for (int s = 0; s < g.spp; ++s) {
+        const size_t k = (size_t)(c * g.spp + s) * 2 * HW + pix;
+        float ut, ur;
+        if (u) { ut = u[k]; ur = u[k + HW]; }
+        else { ut = sensor_uniform(seed, k); ur = sensor_uniform(seed, k + HW); }
+        const float rev = (ut + (float)sec) * (1.f / kRenderAngles);      // theta / (2 pi)
+        const float rr = fsqrt((ur + (float)ring) * g.r2_step);
+        Ray r = ray_to(sx, sy, d_sensor, rr * __builtin_amdgcn_cosf(rev), rr * __builtin_amdgcn_sinf(rev), g.pupil_z);
+        trace_range<false>(tab, 0, n_surf, false, r, nan_flag);
+        const bool live = r.ra > 0.f;
+        if (alive_rays) alive_rays[(size_t)(c * g.spp + s) * HW + pix] = live ? 1 : 0;
+        if (live) {
+            cnt += 1.f;
+            float V[NB], A[NB], T[NB];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) { V[b] = 0.f; A[b] = 0.f; T[b] = 1.f; }
+#pragma unroll 1
+            for (int l = 0; l < lt.L; ++l) {
+                // propagate_to(r, z_l) from the last surface for every plane, and the scene coordinates, with the fusions that the
+                // compiler makes in render_raytraced_kernel written out: here, inside the plane loop, it left vi unfused
+                // (the L = 1 identity is the default build's; a build with -ffp-contract=off fuses nothing over there)
+                const float t = fdiv(lt.z[l] - r.oz, r.dz), inv_texel = lt.inv_texel[l];
+                const float px = __builtin_fmaf(r.dx, t, r.ox), py = __builtin_fmaf(r.dy, t, r.oy);
+                const float uj = __builtin_fmaf(-px, inv_texel, g.cu), vi = __builtin_fmaf(py, inv_texel, g.cv);
+                // NaN-safe: coordinates that are not in the window are never turned into an index
+                const bool ok = (uj >= -1.f) && (uj <= fW) && (vi >= -1.f) && (vi <= fH);
+                if (ok) {
+                    const float fu = floorf(uj), fv = floorf(vi);
+                    const float ax = uj - fu, ay = vi - fv;
+                    const int xi = (int)fu, yi = (int)fv;
+                    const int xa = min(max(xi, 0), g.W - 1), xb = min(max(xi + 1, 0), g.W - 1);       // replicate border
+                    const size_t ra = (size_t)min(max(yi, 0), g.H - 1) * g.W, rb = (size_t)min(max(yi + 1, 0), g.H - 1) * g.W;
+                    {
+#pragma clang fp contract(off)
+                        const float bx = 1.f - ax, by = 1.f - ay;
+#pragma unroll
+                        for (int b = 0; b < NB; ++b) {
+#ifndef AADFF_LAYERED_NO_MAP
+                            const unsigned char* lay = layer + (size_t)b * HW;
+                            const bool m00 = lay[ra + xa] == l, m01 = lay[ra + xb] == l, m10 = lay[rb + xa] == l, m11 = lay[rb + xb] == l;
+#else       // measurement build (the cost of L = 1): every texel on plane 0, the map is not read
+                            const bool m00 = l == 0, m01 = m00, m10 = m00, m11 = m00;
+#endif
+                            if (m00 || m01 || m10 || m11) {               // none of the four on this plane: a = q = 0 exactly, nothing changes
+                                const float* q = im + (size_t)b * 3 * HW;
+                                const float atop = __builtin_fmaf(ax, m01 ? 1.f : 0.f, bx * (m00 ? 1.f : 0.f));
+                                const float abot = __builtin_fmaf(ax, m11 ? 1.f : 0.f, bx * (m10 ? 1.f : 0.f));
+                                const float a = __builtin_fmaf(ay, abot, by * atop);
+                                const float qtop = __builtin_fmaf(ax, m01 ? q[ra + xb] : 0.f, bx * (m00 ? q[ra + xa] : 0.f));
+                                const float qbot = __builtin_fmaf(ax, m11 ? q[rb + xb] : 0.f, bx * (m10 ? q[rb + xa] : 0.f));
+                                const float qv = __builtin_fmaf(ay, qbot, by * qtop);
+                                const float tq = T[b] * qv, ta = T[b] * a;
+                                V[b] = V[b] + tq;
+                                A[b] = A[b] + ta;
+                                T[b] = T[b] * (1.f - a);
+                            }
+                        }
+                    }
+                    bool opaque = true;
+#pragma unroll
+                    for (int b = 0; b < NB; ++b) opaque = opaque && T[b] == 0.f;
+                    if (opaque) break;                                    // nothing behind can add to any image of this launch
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < NB; ++b) { sumV[b] += V[b]; sumA[b] += A[b]; }
+        }
+        if (++ring == g.rings) { ring = 0; ++sec; }
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const float den = vignetting ? (float)g.spp : sumA[b];
+        out[((size_t)b * 3 + c) * HW + pix] = sumA[b] > 0.f ? sumV[b] / den : 0.f;
+        if (coverage) coverage[((size_t)b * 3 + c) * HW + pix] = sumA[b];
+    }
+    if (alive_out) alive_out[(size_t)c * HW + pix] = cnt;
+    if (nan_flag && flags) atomicOr(flags, 1);    // found nan in ft in non-diff newton method (surfaces.py:555-558)
+}
+
 }  // namespace aadff
 
 using namespace aadff;
@@ -1998,6 +2114,73 @@ int aadff_render_raytraced(const float* img, int B, int H, int W, const float* u
 #define AADFF_RENDER_LAUNCH(NB)                                                                                                    \
     hipLaunchKernelGGL(render_raytraced_kernel<NB>, grid, block, 0, (hipStream_t)stream, im, u_or_null, seed, surf_rgb, n_surf, g, \
                        vignetting, state, o, cnt, val, flags_or_null)
+        switch (nb) {
+            case 1: AADFF_RENDER_LAUNCH(1); break;
+            case 2: AADFF_RENDER_LAUNCH(2); break;
+            case 3: AADFF_RENDER_LAUNCH(3); break;
+            default: AADFF_RENDER_LAUNCH(4); break;
+        }
+#undef AADFF_RENDER_LAUNCH
+        AADFF_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int aadff_render_raytraced_layered(const float* img, const unsigned char* layer, int B, int H, int W, const float* u_or_null,
+                                   unsigned long long seed, int spp, const aadff_surface_t* surf_rgb, int n_surf, float pupil_z,
+                                   float pupil_r, float sensor_w, float sensor_h, float pixel_size, int L, const float* layer_depths,
+                                   const float* scales, int vignetting, const aadff_lens_state_t* state, float* out,
+                                   float* coverage_or_null, float* alive_or_null, unsigned char* alive_rays_or_null, int* flags_or_null,
+                                   aadff_stream_t stream) {
+    AADFF_CHECK_ARG(img && layer && surf_rgb && layer_depths && scales && state && out, "render_raytraced_layered: NULL pointer");
+    AADFF_CHECK_ARG(B >= 1 && H >= 1 && W >= 1, "render_raytraced_layered: bad sizes B=%d H=%d W=%d", B, H, W);
+    AADFF_CHECK_ARG(spp > 0 && spp % kRenderAngles == 0,
+                    "render_raytraced_layered: spp=%d must be a positive multiple of %d (stratified pupil samples)", spp, kRenderAngles);
+    AADFF_CHECK_ARG(n_surf > 0 && n_surf <= AADFF_MAX_SURF, "render_raytraced_layered: n_surf %d outside [1,%d]", n_surf, AADFF_MAX_SURF);
+    AADFF_CHECK_ARG(std::isfinite(pupil_z) && std::isfinite(pupil_r) && pupil_r >= 0.f, "render_raytraced_layered: bad pupil (z=%g, r=%g)",
+                    (double)pupil_z, (double)pupil_r);
+    AADFF_CHECK_ARG(std::isfinite(sensor_w) && std::isfinite(sensor_h) && sensor_w > 0.f && sensor_h > 0.f,
+                    "render_raytraced_layered: bad sensor size (%g x %g mm)", (double)sensor_w, (double)sensor_h);
+    AADFF_CHECK_ARG(L >= 1 && L <= AADFF_RENDER_MAX_LAYERS, "render_raytraced_layered: L=%d layers outside [1,%d]", L, AADFF_RENDER_MAX_LAYERS);
+    RenderLayers lt{};
+    lt.L = L;
+    for (int l = 0; l < L; ++l) {
+        const float z = layer_depths[l];
+        AADFF_CHECK_ARG(z < 0.f && std::isfinite(z), "render_raytraced_layered: layer depth %d = %g must be negative (planes in front of the lens)",
+                        l, (double)z);
+        AADFF_CHECK_ARG(l == 0 || z < layer_depths[l - 1],
+                        "render_raytraced_layered: layer depths must be strictly decreasing, nearest first (depth %d = %g after %g)", l, (double)z,
+                        (double)layer_depths[l - 1]);
+        const double texel = (double)scales[l] * (double)pixel_size;
+        AADFF_CHECK_ARG(std::isfinite(texel) && texel > 0.0 && pixel_size > 0.f,
+                        "render_raytraced_layered: scale * pixel_size must be positive (layer %d: scale=%g, pixel_size=%g)", l, (double)scales[l],
+                        (double)pixel_size);
+        lt.z[l] = z;
+        lt.inv_texel[l] = (float)(1.0 / texel);
+    }
+    const unsigned gx = (W + kRenderTile - 1) / kRenderTile, gy = (H + kRenderTile - 1) / kRenderTile;
+    AADFF_CHECK_ARG(gy <= 65535u, "render_raytraced_layered: H=%d exceeds %d rows", H, 65535 * kRenderTile);
+    RenderGeom g;
+    g.H = H; g.W = W; g.spp = spp; g.rings = spp / kRenderAngles;
+    g.pupil_z = pupil_z;
+    g.r2_step = (float)((double)pupil_r * (double)pupil_r / spp * kRenderAngles);
+    g.x0 = (float)(-(double)sensor_w / 2); g.y0 = (float)((double)sensor_h / 2); g.ps = pixel_size;
+    g.depth = lt.z[0]; g.inv_texel = lt.inv_texel[0];                     // not read: the planes come from the table
+    g.cu = (float)(W / 2.0 - 1.0); g.cv = (float)(H / 2.0 - 1.0);
+    const size_t HW = (size_t)H * W;
+    // as in aadff_render_raytraced: every launch traces the same samples for its (up to) kRenderMaxB images and layer maps
+    for (int b0 = 0; b0 < B; b0 += kRenderMaxB) {
+        const int nb = std::min(kRenderMaxB, B - b0);
+        const float* im = img + (size_t)b0 * 3 * HW;
+        const unsigned char* lay = layer + (size_t)b0 * HW;
+        float* o = out + (size_t)b0 * 3 * HW;
+        float* cov = coverage_or_null ? coverage_or_null + (size_t)b0 * 3 * HW : nullptr;
+        float* alive = b0 == 0 ? alive_or_null : nullptr;
+        unsigned char* rays = b0 == 0 ? alive_rays_or_null : nullptr;
+        const dim3 grid(gx, gy, 3), block(kRenderTile * kRenderTile);
+#define AADFF_RENDER_LAUNCH(NB)                                                                                                       \
+    hipLaunchKernelGGL(render_raytraced_layered_kernel<NB>, grid, block, 0, (hipStream_t)stream, im, lay, u_or_null, seed, surf_rgb, \
+                       n_surf, g, lt, vignetting, state, o, cov, alive, rays, flags_or_null)
         switch (nb) {
             case 1: AADFF_RENDER_LAUNCH(1); break;
             case 2: AADFF_RENDER_LAUNCH(2); break;

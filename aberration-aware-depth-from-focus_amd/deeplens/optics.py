@@ -673,6 +673,26 @@ class Lensgroup(DeepObj):
         return raytrace.render_raytraced(self, img, depth=depth, spp=spp, scale=scale, u=u, seed=seed, vignetting=vignetting,
                                          return_aux=return_aux)
 
+    def render_raytraced_layered(self, img, layer, layer_depths, scales=None, spp=64, u=None, seed=None, vignetting=False, return_aux=False):
+        """img [B,3,H,W] with a layer map [B,H,W] over L planes at `layer_depths` (nearest first), ray traced and composited front
+        to back: `aadff.raytrace.render_raytraced_layered`."""
+        from aadff import raytrace
+        return raytrace.render_raytraced_layered(self, img, layer, layer_depths, scales=scales, spp=spp, u=u, seed=seed,
+                                                 vignetting=vignetting, return_aux=return_aux)
+
+    def render_raytraced_rgbd(self, img, depth_mm, layers=8, scales=None, spp=64, u=None, seed=None, vignetting=False, return_aux=False):
+        """img [B,3,H,W] with a depth map (mm < 0), quantised per image by `depth_layers` and rendered as a layered scene ->
+        (out, layer_depths [B,layers]): `aadff.raytrace.render_raytraced_rgbd`."""
+        from aadff import raytrace
+        return raytrace.render_raytraced_rgbd(self, img, depth_mm, layers=layers, scales=scales, spp=spp, u=u, seed=seed,
+                                              vignetting=vignetting, return_aux=return_aux)
+
+    def render_raytraced_layered_stack(self, img, layer, layer_depths, foc_dists, scales=None, spp=64, u=None, seed=None, vignetting=False):
+        """A focal stack [B,3,S,H,W] of layered renders, refocus + render per slice: `aadff.raytrace.render_raytraced_layered_stack`."""
+        from aadff import raytrace
+        return raytrace.render_raytraced_layered_stack(self, img, layer, layer_depths, foc_dists, scales=scales, spp=spp, u=u, seed=seed,
+                                                       vignetting=vignetting)
+
     def _ray_device(self):
         """where the rays of the analysis live: strict / edge lenses keep them on the host (the reference's arithmetic)"""
         return torch.device("cpu") if self.parity != "fast" else self.device

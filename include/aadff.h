@@ -556,6 +556,26 @@ int aadff_render_raytraced(const float* img, int B, int H, int W, const float* u
                            float pixel_size, float depth, float scale, int vignetting, const aadff_lens_state_t* state, float* out,
                            float* count_or_null, unsigned char* valid_or_null, int* flags_or_null, aadff_stream_t stream);
 
+/* Ray-traced rendering of a layered RGB-D scene.  Sensor points, pupil samples, uniforms / seed, trace and scene
+ * coordinates are aadff_render_raytraced's.  The scene is L planes (1 <= L <= AADFF_RENDER_MAX_LAYERS) at layer_depths[l] (HOST
+ * array, mm: 0 > z_0 > z_1 > ... nearest first) with scales[l] (HOST array, object mm per sensor mm at plane l), and layer [B,H,W]
+ * (bytes, device): the plane each texel of image b lies on; an index >= L lies on none (a hole).  Both host arrays are copied into the
+ * kernel arguments by the call.  Every ray that survived the lens starts with T = 1, A = 0, V = 0 per image and visits l = 0 .. L-1:
+ * propagated from its last surface to z_l it meets the plane if -1 <= uj <= W, -1 <= vi <= H (coordinates with scales[l]); with the
+ * four texels and bilinear weights of aadff_render_raytraced, a = the bilinear form of m_t = (layer[b,t] == l), q = the same form of
+ * (m_t ? img[b,c,t] : 0); then V += T q, A += T a, T *= 1 - a.  out [B,3,H,W] = sum V / sum A over the pixel's rays, 0 where sum A = 0;
+ * with vignetting != 0 sum V / spp.  coverage_or_null [B,3,H,W] = sum A; alive_or_null [3,H,W] the rays that survived the lens (float);
+ * alive_rays_or_null [3,spp,H,W] bytes, per ray (diagnostics).  With L = 1 and layer == 0 the output equals aadff_render_raytraced's bit
+ * for bit and coverage its count.  No atomics: bit-reproducible; B > 4 runs as launches of 4 images over the same rays, an image
+ * renders to the same bits in any of them.  flags bit 0: NaN in a Newton residual. */
+#define AADFF_RENDER_MAX_LAYERS 32
+int aadff_render_raytraced_layered(const float* img, const unsigned char* layer, int B, int H, int W, const float* u_or_null,
+                                   unsigned long long seed, int spp, const aadff_surface_t* surf_rgb, int n_surf, float pupil_z,
+                                   float pupil_r, float sensor_w, float sensor_h, float pixel_size, int L, const float* layer_depths,
+                                   const float* scales, int vignetting, const aadff_lens_state_t* state, float* out,
+                                   float* coverage_or_null, float* alive_or_null, unsigned char* alive_rays_or_null, int* flags_or_null,
+                                   aadff_stream_t stream);
+
 /* The uniforms aadff_render_raytraced draws when it is given none: out [3,spp,2,H,W], element idx = output idx of the SplitMix64
  * sequence seeded with `seed` (z = seed + (idx+1) 0x9E3779B97F4A7C15; z = (z ^ z>>30) 0xBF58476D1CE4E5B9; z = (z ^ z>>27)
  * 0x94D049BB133111EB; z ^= z>>31), its top 24 bits times 2^-24: values in [0, 1). */
