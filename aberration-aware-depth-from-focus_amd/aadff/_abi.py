@@ -126,6 +126,7 @@ PROTOTYPES = {
     "aadff_trace_points": [_P, _I, _P, _P, _I, _F, _F, _P, _I, _P, _P, _P, _P, _P],
     "aadff_psf_splat": [_P, _P, _P, _I, _I, _F, _I, _P, _P, _P],
     "aadff_spot_moments": [_P, _I, _P, _I, _I, _I, _P, _I, _F, _F, _P, _I, _I, _P, _P, _P],
+    "aadff_mtf_points": [_P, _I, _P, _I, _I, _I, _P, _I, _F, _F, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P],
     "aadff_render_raytraced": [_P, _I, _I, _I, _P, C.c_ulonglong, _I, _P, _I, _F, _F, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P, _P],
     "aadff_sensor_uniforms": [C.c_ulonglong, _I, _I, _I, _P, _P],
     "aadff_render_raytraced_layered": [_P, _P, _I, _I, _I, _P, C.c_ulonglong, _I, _P, _I, _F, _F, _F, _F, _F, _I, _P, _P, _I, _P, _P, _P, _P, _P,

@@ -1584,6 +1584,163 @@ __global__ __launch_bounds__(kSpotThreads) void spot_moments_kernel(const float*
 }
 
 // ------------------------------------------------------------------------------------
+// Ray-traced MTF: the geometric OTF as the Fourier transform of the traced hits themselves - no histogram, no
+// window.  Phase 1 is spot_moments_kernel's (same draws, same pupil points, same trace, same order of sums), except that every
+// ray's hit (x, y) at d_sensor, its slopes (a, b) = (dx/dz, dy/dz) behind the last surface and its validity stay in LDS.  Behind
+// the lens a ray is a straight line, so on the plane d_sensor + delta it lands at (x + a delta, y + b delta): a sensor plane costs
+// one multiply-add per coordinate.  Between the phases the valid rays are moved to the front of the LDS array in index order
+// (a prefix count over the validity words) with the pass's means subtracted: the phase is formed from the small centred
+// coordinates.  Phase 2: one lane owns one output entry (delta, axis, nu), walks those rays in order (every lane reads the same
+// LDS address: a broadcast; a counted loop, so the reads of the next rays are in flight while this one is used) and adds cos /
+// sin of 2 pi nu e.(h - c) into its own two registers.  No cross-lane sum in phase 2, no atomics, every output written once: a
+// launch is bit-reproducible.
+// ------------------------------------------------------------------------------------
+constexpr int kMtfMaxSpp = 2 * kSpotThreads * kSpotMaxPairs;      // 2048 rays x 16 B = 32 KB of LDS
+constexpr int kMtfMaxF = 128, kMtfMaxZ = 16;
+struct MtfGrid { float freq[kMtfMaxF]; float defocus[kMtfMaxZ]; };  // copied into the kernel arguments by the call
+
+__global__ __launch_bounds__(kSpotThreads) void mtf_points_kernel(const float* __restrict__ points, int P, const float* __restrict__ u,
+                                                                  int spp, int num_angle, int n_pass,
+                                                                  const aadff_surface_t* __restrict__ surf, int n_surf, float pupil_z,
+                                                                  float r2_step, const aadff_lens_state_t* __restrict__ state,
+                                                                  const MtfGrid grid, int F, int Z, int axes_mode,
+                                                                  float2* __restrict__ otf, float* __restrict__ moments, int* flags) {
+    __shared__ float4 hit[kMtfMaxSpp];                     // (x, y, a, b) of ray s; before phase 2 the valid ones, centred, in index order
+    __shared__ unsigned alive_bits[kMtfMaxSpp / 32];       // bit s % 32 of word s / 32: ray s is valid
+    __shared__ unsigned short before[kMtfMaxSpp / 32];     // valid rays in the words before word w
+    __shared__ int n_alive;
+    __shared__ float red[5 * kSpotWaves];
+    __shared__ float mean[5];                              // x, y, a, b means and the valid count
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const float d_sensor = fresh_uniform(&state->d_sensor);
+    const float px = points[3 * p], py = points[3 * p + 1], pz = points[3 * p + 2];
+    // tangential axis: the direction of the object point itself, an input (a computed centroid's direction is noise near the axis)
+    float tx = 1.f, ty = 0.f;
+    if (axes_mode == 0 && (px != 0.f || py != 0.f)) {
+        const float h = sqrtf(px * px + py * py);
+        tx = px / h; ty = py / h;
+    }
+    const int rings = spp / num_angle;
+    const float inv_a = 1.f / (float)num_angle;
+    const int n_iter = (spp + 2 * kSpotThreads - 1) / (2 * kSpotThreads);
+    const int E = Z * 2 * F;
+    int nan_flag = 0;
+    for (int q = 0; q < n_pass; ++q) {
+        const float* uq = u + (size_t)q * 2 * spp * P;
+        const aadff_surface_t* tab = surf + (size_t)q * n_surf;
+        float sx = 0.f, sy = 0.f, sa = 0.f, sb = 0.f, sn = 0.f;
+#pragma unroll 1
+        for (int k = 0; k < n_iter; ++k) {
+            const int s0 = tid + k * 2 * kSpotThreads;
+            if (s0 >= spp) break;
+            const int s1 = s0 + kSpotThreads;
+            const i2 act = {-1, s1 < spp ? -1 : 0};
+            const int sb_ = act.y ? s1 : s0;
+            const int i0 = s0 / rings, ib = sb_ / rings;
+            const f2 ut = {uq[(size_t)(2 * s0) * P + p], uq[(size_t)(2 * sb_) * P + p]};
+            const f2 ur = {uq[(size_t)(2 * s0 + 1) * P + p], uq[(size_t)(2 * sb_ + 1) * P + p]};
+            const f2 rev = (ut + (f2){(float)i0, (float)ib}) * inv_a;                       // theta / (2 pi)
+            const f2 rr = vsqrt((ur + (f2){(float)(s0 - i0 * rings), (float)(sb_ - ib * rings)}) * r2_step);
+            const f2 x2 = rr * (f2){__builtin_amdgcn_cosf(rev.x), __builtin_amdgcn_cosf(rev.y)};
+            const f2 y2 = rr * (f2){__builtin_amdgcn_sinf(rev.x), __builtin_amdgcn_sinf(rev.y)};
+            const Ray2 r = trace_pair_to_sensor(px, py, pz, x2, y2, pupil_z, act, tab, n_surf, d_sensor, nan_flag);
+            const f2 iz = vrcp(r.dz);
+            const f2 wx = vsel(r.alive, r.ox, f2s(0.f)), wy = vsel(r.alive, r.oy, f2s(0.f));
+            const f2 wa = vsel(r.alive, r.dx * iz, f2s(0.f)), wb = vsel(r.alive, r.dy * iz, f2s(0.f));
+            sx += wx.x + wx.y; sy += wy.x + wy.y;
+            sa += wa.x + wa.y; sb += wb.x + wb.y;
+            sn += (r.alive.x ? 1.f : 0.f) + (r.alive.y ? 1.f : 0.f);
+            hit[s0] = make_float4(wx.x, wy.x, wa.x, wb.x);
+            if (act.y) hit[s1] = make_float4(wx.y, wy.y, wa.y, wb.y);
+            // a wave's 64 first rays (and its 64 second rays) are consecutive and start at a multiple of 64: two words each.  Lane 0
+            // of a wave has the wave's smallest s0, so it is here whenever any lane of the wave is.
+            const unsigned long long b0 = __ballot(r.alive.x != 0), b1 = __ballot(r.alive.y != 0);
+            if ((tid & 63) == 0) {
+                alive_bits[s0 >> 5] = (unsigned)b0; alive_bits[(s0 >> 5) + 1] = (unsigned)(b0 >> 32);
+                alive_bits[s1 >> 5] = (unsigned)b1; alive_bits[(s1 >> 5) + 1] = (unsigned)(b1 >> 32);
+            }
+        }
+        sx = wave_sum(sx); sy = wave_sum(sy); sa = wave_sum(sa); sb = wave_sum(sb); sn = wave_sum(sn);
+        if ((tid & 63) == 0) {
+            float* w = red + (tid >> 6) * 5;
+            w[0] = sx; w[1] = sy; w[2] = sa; w[3] = sb; w[4] = sn;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            sx = sy = sa = sb = sn = 0.f;
+            for (int w = 0; w < kSpotWaves; ++w) {
+                sx += red[5 * w]; sy += red[5 * w + 1]; sa += red[5 * w + 2]; sb += red[5 * w + 3]; sn += red[5 * w + 4];
+            }
+            float* m = moments + ((size_t)q * P + p) * 8;
+            m[0] = sn; m[1] = sx; m[2] = sy; m[3] = sa; m[4] = sb; m[5] = 0.f; m[6] = 0.f; m[7] = 0.f;
+            const float den = sn > 0.f ? sn : 1.f;          // plain means: no + 1e-4 (this is not analysis_rms's centroid)
+            mean[0] = sx / den; mean[1] = sy / den; mean[2] = sa / den; mean[3] = sb / den; mean[4] = sn;
+        }
+        if (tid < 64) {                           // valid rays before word tid: an inclusive scan over wave 0, less the word's own
+            const unsigned c = tid < (spp + 31) / 32 ? __popc(alive_bits[tid]) : 0u;
+            unsigned incl = c;
+            for (int d = 1; d < 64; d <<= 1) {
+                const unsigned v = __shfl_up(incl, d);
+                if (tid >= d) incl += v;
+            }
+            before[tid] = (unsigned short)(incl - c);
+            if (tid == 63) n_alive = (int)incl;
+        }
+        __syncthreads();
+        const float n_valid = mean[4];
+        const int n_rays = __builtin_amdgcn_readfirstlane(n_alive);
+        {
+            // the valid rays move to the front in index order, centred: phase 2 then runs a counted loop over 0 .. n - 1
+            const float mx = mean[0], my = mean[1], ma = mean[2], mb = mean[3];
+            float4 keep[2 * kSpotMaxPairs];
+            int dest[2 * kSpotMaxPairs];
+#pragma unroll
+            for (int i = 0; i < 2 * kSpotMaxPairs; ++i) {                  // constant register indices
+                const int s = tid + i * kSpotThreads;
+                dest[i] = -1;
+                keep[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (s < spp) {
+                    const unsigned w = alive_bits[s >> 5], bit = 1u << (s & 31);
+                    if (w & bit) {
+                        const float4 h = hit[s];
+                        keep[i] = make_float4(h.x - mx, h.y - my, h.z - ma, h.w - mb);
+                        dest[i] = (int)before[s >> 5] + __popc(w & (bit - 1u));
+                    }
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < 2 * kSpotMaxPairs; ++i)
+                if (dest[i] >= 0) hit[dest[i]] = keep[i];
+        }
+        __syncthreads();
+        // phase 2: entry e = (z * 2 + axis) * F + f; every lane runs every trip (the ray loop is wave-uniform), the store is masked
+        for (int base = 0; base < E; base += kSpotThreads) {
+            if (base + (tid & ~63) >= E) continue;                         // a wave without an entry leaves its SIMD to the others
+            const int e = min(base + tid, E - 1);
+            const int za = e / F, f = e - za * F, axis = za & 1, z = za >> 1;
+            const float nu = grid.freq[f], dl = grid.defocus[z];
+            const float ex = axis ? -ty : tx, ey = axis ? tx : ty;     // e_T, or e_S = (-e_T.y, e_T.x)
+            float re = 0.f, im = 0.f;
+#pragma unroll 4
+            for (int k = 0; k < n_rays; ++k) {
+                const float4 h = hit[k];
+                const float t = ex * (h.x + h.z * dl) + ey * (h.y + h.w * dl);         // e . (h(delta) - c(delta)), mm
+                const float rv = __builtin_amdgcn_fractf(nu * t);                       // revolutions, reduced to [0, 1)
+                re += __builtin_amdgcn_cosf(rv);
+                im -= __builtin_amdgcn_sinf(rv);                                        // exp(-2 pi i nu t)
+            }
+            if (base + tid < E) {
+                const bool any = n_valid > 0.f;
+                otf[((size_t)q * P + p) * E + e] = make_float2(any ? re / n_valid : 0.f, any ? im / n_valid : 0.f);
+            }
+        }
+        __syncthreads();                          // hit / alive_bits / before / red / mean are rewritten by the next pass
+    }
+    if (nan_flag && flags) atomicOr(flags, 1);    // found nan in ft in non-diff newton method (surfaces.py:555-558)
+}
+
+// ------------------------------------------------------------------------------------
 // Ray-traced image rendering: sensor pixel -> exit pupil -> backwards through the lens -> object plane ->
 // bilinear sample of the scene.  One lane owns one (pixel, channel): it loops over the spp samples and keeps the valid
 // count and the running sums of up to kRenderMaxB images in registers (the rays do not depend on the image), so there is
@@ -2060,6 +2217,37 @@ int aadff_spot_moments(const float* points, int P, const float* u, int spp, int 
     const float r2_step = (float)((double)pupil_r * (double)pupil_r / spp * num_angle);     // pupilr**2 / spp * num_angle
     hipLaunchKernelGGL(spot_moments_kernel, dim3(P), dim3(kSpotThreads), 0, (hipStream_t)stream, points, P, u, spp, num_angle, n_pass,
                        surf, n_surf, pupil_z, r2_step, state, ref_mode, want_s2, reinterpret_cast<float4*>(moments), flags_or_null);
+    AADFF_CHECK_LAUNCH();
+    return 0;
+}
+
+int aadff_mtf_points(const float* points, int P, const float* u, int spp, int num_angle, int n_pass, const aadff_surface_t* surf,
+                     int n_surf, float pupil_z, float pupil_r, const aadff_lens_state_t* state, const float* freqs, int F,
+                     const float* defocus, int Z, int axes_mode, float* otf, float* moments, int* flags_or_null, aadff_stream_t stream) {
+    AADFF_CHECK_ARG(points && u && surf && state && freqs && defocus && otf && moments, "mtf_points: NULL pointer");
+    AADFF_CHECK_ARG(P > 0 && P <= (1 << 20) && n_pass > 0 && n_pass <= 16, "mtf_points: bad sizes P=%d n_pass=%d", P, n_pass);
+    AADFF_CHECK_ARG(n_surf > 0 && n_surf <= AADFF_MAX_SURF, "mtf_points: n_surf %d outside [1,%d]", n_surf, AADFF_MAX_SURF);
+    AADFF_CHECK_ARG(num_angle > 0 && spp > 0 && spp % num_angle == 0 && spp <= kMtfMaxSpp,
+                    "mtf_points: spp=%d must be a positive multiple of num_angle=%d and at most %d (stratified pupil samples, kept in LDS)",
+                    spp, num_angle, kMtfMaxSpp);
+    AADFF_CHECK_ARG(F >= 1 && F <= kMtfMaxF, "mtf_points: F=%d frequencies outside [1,%d]", F, kMtfMaxF);
+    AADFF_CHECK_ARG(Z >= 1 && Z <= kMtfMaxZ, "mtf_points: Z=%d sensor planes outside [1,%d]", Z, kMtfMaxZ);
+    AADFF_CHECK_ARG(axes_mode == 0 || axes_mode == 1, "mtf_points: axes_mode %d is 0 (radial) or 1 (xy)", axes_mode);
+    AADFF_CHECK_ARG(std::isfinite(pupil_z) && std::isfinite(pupil_r) && pupil_r >= 0.f, "mtf_points: bad pupil (z=%g, r=%g)",
+                    (double)pupil_z, (double)pupil_r);
+    MtfGrid grid = {};
+    for (int f = 0; f < F; ++f) {
+        AADFF_CHECK_ARG(std::isfinite(freqs[f]) && freqs[f] >= 0.f, "mtf_points: frequency %d = %g is not finite and >= 0", f, (double)freqs[f]);
+        grid.freq[f] = freqs[f];
+    }
+    for (int z = 0; z < Z; ++z) {
+        AADFF_CHECK_ARG(std::isfinite(defocus[z]), "mtf_points: defocus %d = %g is not finite", z, (double)defocus[z]);
+        grid.defocus[z] = defocus[z];
+    }
+    const float r2_step = (float)((double)pupil_r * (double)pupil_r / spp * num_angle);     // pupilr**2 / spp * num_angle
+    hipLaunchKernelGGL(mtf_points_kernel, dim3(P), dim3(kSpotThreads), 0, (hipStream_t)stream, points, P, u, spp, num_angle, n_pass,
+                       surf, n_surf, pupil_z, r2_step, state, grid, F, Z, axes_mode, reinterpret_cast<float2*>(otf), moments,
+                       flags_or_null);
     AADFF_CHECK_LAUNCH();
     return 0;
 }

@@ -730,6 +730,14 @@ class Lensgroup(DeepObj):
         d = d / torch.linalg.vector_norm(d, ord=2, dim=-1, keepdim=True)
         return Ray(o, d, wvln, device=dev)
 
+    def _uniform_block(self, n_u):
+        """the next n_u draws of `self.sampler` on the GPU, as one flat block (host samplers: through pinned memory)"""
+        dev = self._gpu()
+        if self.sampler.on_device:
+            return self.sampler.rand_block([n_u]).to(dev)
+        host = torch.empty(n_u, dtype=torch.float32, pin_memory=True)
+        return self.sampler.rand_into(host).to(dev, non_blocking=True)
+
     def _spot_moments(self, points, depth_wvlns, spp, ref_mode, want_s2, num_angle=8):
         """aadff_spot_moments: [n_pass, P, 4] = (valid count, sum x, sum y, S2) per pass and object point (points [P,3]).
         Draws: one block of n_pass * 2 * spp * P uniforms from `self.sampler`, i.e. the reference's sample_pupil calls of the
@@ -738,12 +746,7 @@ class Lensgroup(DeepObj):
         P, L = points.shape[0], len(depth_wvlns)
         pupilz, pupilr = self.entrance_pupil()
         st = self._state_device()
-        n_u = L * 2 * spp * P
-        if self.sampler.on_device:
-            u = self.sampler.rand_block([n_u]).to(dev)
-        else:
-            host = torch.empty(n_u, dtype=torch.float32, pin_memory=True)
-            u = self.sampler.rand_into(host).to(dev, non_blocking=True)
+        u = self._uniform_block(L * 2 * spp * P)
         pts = _abi.f32c(points, dev)
         mom = torch.empty((L, P, 4), dtype=torch.float32, device=dev)
         with _abi.on_device(dev):
@@ -876,6 +879,38 @@ class Lensgroup(DeepObj):
         plt.savefig(save_name, bbox_inches="tight", format="png", dpi=300)
         plt.close()
         return save_name
+
+    # ------------------------------------------------------------------ ray-traced MTF and distortion (aadff.mtf)
+    def mtf(self, points, freqs, wvlns=WAVE_RGB, defocus=(0.,), spp=GEO_SPP, axes="radial"):
+        """Ray-traced MTF at normalised field points [P,3] -> (mtf [P,L,Z,2,F], complex otf, centroid [P,L,Z,2], count [P,L]):
+        `aadff.mtf.mtf` (one fused launch; no counterpart in the reference, whose psf2mtf cuts a histogram)."""
+        from aadff import mtf as _mtf
+        return _mtf.mtf(self, points, freqs, wvlns=wvlns, defocus=defocus, spp=spp, axes=axes)
+
+    def mtf_through_focus(self, point, freq, span, steps, wvln=DEFAULT_WAVE, spp=GEO_SPP, axes="radial"):
+        """(delta [steps], curve [steps,2], peak [2]) of one field point at one frequency over sensor shifts: `aadff.mtf.mtf_through_focus`."""
+        from aadff import mtf as _mtf
+        return _mtf.mtf_through_focus(self, point, freq, span, steps, wvln=wvln, spp=spp, axes=axes)
+
+    def psf2mtf(self, psf, diag=False):
+        """(freq, tangential_mtf, sagittal_mtf) of a 2-D PSF by FFT (reference: optics.py:1028-1065): `aadff.mtf.psf2mtf`."""
+        from aadff import mtf as _mtf
+        return _mtf.psf2mtf(self, psf, diag=diag)
+
+    def draw_mtf(self, relative_fov=[0.0, 0.7, 1.0], save_name="./mtf.png", wvlns=DEFAULT_WAVE, depth=DEPTH):
+        """MTF curves at diagonal field points, the reference's figure (optics.py:1914-1941) from the ray-traced MTF: `aadff.mtf.draw_mtf`."""
+        from aadff import mtf as _mtf
+        return _mtf.draw_mtf(self, relative_fov=relative_fov, save_name=save_name, wvlns=wvlns, depth=depth)
+
+    def distortion_grid(self, depth=DEPTH, M=16):
+        """(ideal [M,M,2], traced [M,M,2]) sensor positions of an M x M object grid (reference: optics.py:1944-1959): `aadff.mtf.distortion_grid`."""
+        from aadff import mtf as _mtf
+        return _mtf.distortion_grid(self, depth=depth, M=M)
+
+    def draw_distortion(self, depth=DEPTH, save_name=None):
+        """The reference's distortion figure (optics.py:1944-1972): `aadff.mtf.draw_distortion`."""
+        from aadff import mtf as _mtf
+        return _mtf.draw_distortion(self, depth=depth, save_name=save_name)
 
     # ------------------------------------------------------------------ PSFs
     def point_source_grid(self, depth, grid=9, normalized=True, quater=False, center=False):

@@ -538,6 +538,23 @@ int aadff_spot_moments(const float* points, int P, const float* u, int spp, int 
                        const aadff_lens_state_t* state, int ref_mode, int want_s2, float* moments,
                        int* flags_or_null, aadff_stream_t stream);
 
+/* Ray-traced MTF: the geometric OTF of every object point, colour, sensor plane, axis and frequency in one launch.
+ * Stands for psf2mtf and draw_mtf (deeplens/optics.py:1028-1065, 1914-1941), which cut one row and one column out of a 256 x 256
+ * psf_diff histogram and FFT them; here the transform is taken of the traced hits themselves.  points, u, spp, num_angle, n_pass,
+ * surf, pupil and state are aadff_spot_moments': the same rays on the same draws.  Per pass q and point p, the n valid rays land at
+ * (x_k, y_k) on z = d_sensor with slopes a_k = dx/dz, b_k = dy/dz; on the plane d_sensor + defocus[z] (HOST array, mm, Z <= 16) they
+ * land at h_k = (x_k + a_k delta, y_k + b_k delta) around c = (mean x + mean a delta, mean y + mean b delta), plain means over the
+ * valid rays.  Axes: axes_mode 0 (radial) e_T = (p_x, p_y) / hypot(p_x, p_y) of the object point ((1, 0) when both are exactly 0),
+ * e_S = (-e_T.y, e_T.x); axes_mode 1 (xy) e_T = (1, 0), e_S = (0, 1).  For freqs[f] (HOST array, cycles/mm, finite and >= 0,
+ * F <= 128): OTF = (1/n) sum_k exp(-2 pi i nu e.(h_k - c)), zeros when n = 0.  Both host arrays are copied into the kernel
+ * arguments by the call.  Out: otf [n_pass][P][Z][2 (T, S)][F][2 (re, im)]; moments [n_pass][P][8] = (n, sum x, sum y, sum a,
+ * sum b, 0, 0, 0), the first three summed in aadff_spot_moments' order.  One workgroup per point, rays kept in LDS (spp <= 2048), one
+ * lane per output entry, no atomics: bit-reproducible.  flags bit 0: NaN in a Newton residual. */
+int aadff_mtf_points(const float* points, int P, const float* u, int spp, int num_angle, int n_pass,
+                     const aadff_surface_t* surf, int n_surf, float pupil_z, float pupil_r,
+                     const aadff_lens_state_t* state, const float* freqs, int F, const float* defocus, int Z,
+                     int axes_mode, float* otf, float* moments, int* flags_or_null, aadff_stream_t stream);
+
 /* Ray-traced image rendering (no counterpart in the reference snapshot, whose 'raytracing' branch of
  * render_single_img calls methods it does not define).  For every pixel (i, j) of an H x W sensor and every channel c (surf_rgb
  * [3][n_surf]: the tables of WAVE_RGB), spp rays leave the sensor point (-sensor_w/2 + (j+1) ps, sensor_h/2 - (i+1) ps, d_sensor)
