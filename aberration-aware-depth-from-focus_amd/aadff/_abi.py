@@ -19,6 +19,7 @@ SURF_STOP, SURF_SPHERIC, SURF_ASPHERIC = 0, 1, 2
 DFOCUS_INTERP = {"none": 0, "parabola": 1, "gaussian": 2}        # AADFF_DFOCUS_*
 VALID_MODES = {"mask": 0, "finite": 1}                           # AADFF_VALID_*
 DEPTH_METRIC_COLS, SSIM_TILE_H, SSIM_TILE_W = 16, 32, 64         # AADFF_DEPTH_METRIC_COLS, AADFF_SSIM_TILE_*
+CHIEF_NODES, CHIEF_RAYS, CHIEF_DEGREE, CHIEF_FIT_TOL = 85, 128, 10, 1e-6     # AADFF_CHIEF_*: the chief-centre fit
 
 
 class Surface(C.Structure):
@@ -134,6 +135,11 @@ PROTOTYPES = {
     "aadff_psf_points": [_P, _I, _I, _I, _P, _P, LensConst, _P, _P, _I, _L, _L, _P, _I, _L, _L, _I, _I, _I, _P, _P, _P, _P],
     "aadff_psf_points_staged": [_P, _I, _I, _I, _P, _P, LensConst, _P, _P, _I, _L, _L, _P, _I, _L, _L, _I, _I, _I, _P, _P, _P,
                                 C.POINTER(Stage), _P],
+    "aadff_chief_fit_weights": [_P, _I, _I, _I, _L, _L, C.POINTER(Stage), _P, _P],
+    "aadff_psf_points_fit": [_P, _I, _I, _I, _P, _P, LensConst, _P, _P, _I, _L, _L, _P, _I, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "aadff_psf_points_staged_fit": [_P, _I, _I, _I, _P, _P, LensConst, _P, _P, _I, _L, _L, _P, _I, _L, _L, _I, _I, _I, _P, _P, _P,
+                                    C.POINTER(Stage), _P, _P, _P],
+    "aadff_chief_fit_tables": [_P, _P, _P],
     "aadff_psf_points_edge": [_P, _I, _I, _I, _P, _P, LensConst, _P, _P, _I, _L, _L, _P, _I, _L, _L, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P],
     "aadff_strict_edge_retrace": [_P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _I, _P, _F, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],
     "aadff_psf_normalise": [_P, _I, _I, _I, _F, _I, _I, _P, _P],

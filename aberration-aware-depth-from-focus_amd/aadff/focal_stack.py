@@ -69,6 +69,9 @@ def draw_stack_uniforms(sampler, S, spp, L=3, spp_chief=GEO_SPP, spp_focus=GEO_S
 
 
 STAGED_UPLOAD = os.environ.get("AADFF_STAGED_UPLOAD", "1") != "0"
+# chief centres of unvignetted points from 128 node rays instead of 2048 chief rays; AADFF_CHIEF_FIT=0: every
+# centre from all draws (a fitted centre is this draw's sample mean to 3e-6 mm, the float32 noise of that mean, not to the bit)
+CHIEF_FIT = os.environ.get("AADFF_CHIEF_FIT", "1") != "0"
 # staged path: focus traces of a stack on the plan's side stream, beside the previous stack's kernels.  Opt-in: +1-3 % of
 # throughput, but in ~1 of 6 stacks the traces land beside the convolution, whose own duration then reads ~5 us longer -
 # the default keeps every kernel alone on the device so that per-kernel measurements mean what they say.
@@ -86,7 +89,7 @@ class StackPlan:
     RING = 8           # pinned/device uniform blocks in flight
     GUARD_EVERY = 4    # staged path: one guard event per 4 steps protects the reuse of a pinned block RING steps later
 
-    def __init__(self, lens, S, H, W, B=1, C_=3, grid=11, ks=11, spp=GEO_SPP, overlap_refocus=None):
+    def __init__(self, lens, S, H, W, B=1, C_=3, grid=11, ks=11, spp=GEO_SPP, overlap_refocus=None, chief_fit=None):
         dev = lens._gpu()
         self.lens, self.S, self.grid, self.ks, self.spp, self.dev = lens, S, grid, ks, spp, dev
         # focus states, one block per ring slot: the focus traces of stack i+1 run on a side stream WHILE the PSF-grid and
@@ -124,6 +127,10 @@ class StackPlan:
         self.stage_counters = torch.zeros(S, dtype=torch.int32, device=dev)
         self.refocus_scratch = torch.zeros(S * 16, dtype=torch.int32, device=dev)     # 64 B per focus state
         self.stage_generation = 0
+        # chief-centre fit (aadff_chief_fit_weights -> aadff_psf_points_fit): the weights and node-ray centres of this plan's stack in flight
+        self.chief_fit = CHIEF_FIT if chief_fit is None else bool(chief_fit)
+        self.fit_weights = torch.empty(S * 3 * 2 * _abi.CHIEF_NODES, dtype=torch.float32, device=dev) if self.chief_fit else None
+        self.fit_centres = torch.empty(S * 3 * grid * grid * 4, dtype=torch.float32, device=dev) if self.chief_fit else None
         self._geo = {}
 
     def uniforms(self, sampler):
@@ -309,16 +316,22 @@ def render_focal_stack_m1(lens, img, depth_plane_mm, focus_mm, grid=11, ks=11, s
             plan.psf_events[0].record()
         if plan.psf_kernel_events is not None:
             _abi.call("aadff_time_next_launch", C.c_void_p(plan.psf_kernel_events[0].cuda_event), C.c_void_p(plan.psf_kernel_events[1].cuda_event))
+        # plan.chief_fit: chief centres from the node rays where no chief ray is vignetted, the weights of this stack's
+        # draws first; without it the fit entries get no buffers and are aadff_psf_points / _staged.  (The kernel events attached above
+        # go to the PSF-grid kernel alone: the weights and node-ray launches, 40 us, lie in front of them; plan.psf_events has all three.)
+        if plan.chief_fit:
+            _abi.call("aadff_chief_fit_weights", C.c_void_p(ub + 4 * plan.o_chief), S, 3, GEO_SPP, plan.per, plan.per_l,
+                      None if stage is None else C.byref(stage), _abi.ptr(plan.fit_weights), st)
         if stage is None:
-            _abi.call("aadff_psf_points", _abi.ptr(pts), S, N, 3, _abi.ptr(plan.tab_rgb), _abi.ptr(plan.tab_green),
+            _abi.call("aadff_psf_points_fit", _abi.ptr(pts), S, N, 3, _abi.ptr(plan.tab_rgb), _abi.ptr(plan.tab_green),
                       plan.lc, _abi.ptr(plan.states), C.c_void_p(ub + 4 * plan.o_main), spp, plan.per, plan.per_l,
                       C.c_void_p(ub + 4 * plan.o_chief), GEO_SPP, plan.per, plan.per_l, ks, 1, 1,
-                      _abi.ptr(plan.psf_maps), None, _abi.ptr(plan.flags), st)
+                      _abi.ptr(plan.psf_maps), None, _abi.ptr(plan.flags), _abi.ptr(plan.fit_weights), _abi.ptr(plan.fit_centres), st)
         else:
-            _abi.call("aadff_psf_points_staged", _abi.ptr(pts), S, N, 3, _abi.ptr(plan.tab_rgb), _abi.ptr(plan.tab_green),
+            _abi.call("aadff_psf_points_staged_fit", _abi.ptr(pts), S, N, 3, _abi.ptr(plan.tab_rgb), _abi.ptr(plan.tab_green),
                       plan.lc, _abi.ptr(plan.states), C.c_void_p(ub + 4 * plan.o_main), spp, plan.per, plan.per_l,
                       C.c_void_p(ub + 4 * plan.o_chief), GEO_SPP, plan.per, plan.per_l, ks, 1, 1,
-                      _abi.ptr(plan.psf_maps), None, _abi.ptr(plan.flags), C.byref(stage), st)
+                      _abi.ptr(plan.psf_maps), None, _abi.ptr(plan.flags), C.byref(stage), _abi.ptr(plan.fit_weights), _abi.ptr(plan.fit_centres), st)
         if plan.psf_events is not None:
             plan.psf_events[1].record()
         if plan.conv_events is not None:
@@ -454,9 +467,14 @@ def render_focal_stack_m1_layered(lens, img, depth_mm, focus_mm, layers=4, grid=
         st_rep = states.view(S, nb).repeat_interleave(L, 0).contiguous()
         u_pairs = u.view(S, slice_stride)[:, o_main:].contiguous()
         base = u_pairs.data_ptr()
-        _abi.call("aadff_psf_points", _abi.ptr(pts), S * L, N, 3, _abi.ptr(tab_rgb), _abi.ptr(tab_green), lc, _abi.ptr(st_rep),
+        fit_w = fit_c = None
+        if CHIEF_FIT:       # chief centres of the unvignetted points from the node rays, as on the plan path
+            fit_w = torch.empty(S * L * 3 * 2 * _abi.CHIEF_NODES, dtype=torch.float32, device=dev)
+            fit_c = torch.empty(S * L * 3 * N * 4, dtype=torch.float32, device=dev)
+            _abi.call("aadff_chief_fit_weights", C.c_void_p(base + 4 * 2 * spp), S * L, 3, GEO_SPP, layer_block, per_l, None, _abi.ptr(fit_w), st)
+        _abi.call("aadff_psf_points_fit", _abi.ptr(pts), S * L, N, 3, _abi.ptr(tab_rgb), _abi.ptr(tab_green), lc, _abi.ptr(st_rep),
                   C.c_void_p(base), spp, layer_block, per_l, C.c_void_p(base + 4 * 2 * spp), GEO_SPP, layer_block, per_l, ks, 1, 1,
-                  _abi.ptr(maps), None, _abi.ptr(flags), st)
+                  _abi.ptr(maps), None, _abi.ptr(flags), _abi.ptr(fit_w), _abi.ptr(fit_c), st)
         if ks == 11 and fused:
             # the L candidates of a pixel are computed from one staged band and only the pixel's own layer is written: 1 x the output
             lidx = idx.reshape(B, H, W).to(torch.uint8).contiguous()

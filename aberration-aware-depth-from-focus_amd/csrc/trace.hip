@@ -14,6 +14,7 @@
 #include <cstring>
 #include <hip/hip_ext.h>
 #include "common.h"
+#include "chief_fit_tables.h"
 
 namespace aadff {
 
@@ -781,6 +782,112 @@ __device__ __forceinline__ Ray2 trace_pair_to_sensor(float px, float py, float p
 }
 
 // ------------------------------------------------------------------------------------
+// Chief-centre fit.  The chief centre of a field point is the mean, over the spp_chief drawn points of the shrunk
+// pupil, of the sensor hit - a smooth function of the pupil position, i.e. a low-order polynomial where no ray is vignetted.  The
+// mean of a polynomial over the draws is sum_k w_k p(node_k) for fixed nodes, with w = pinv(V)^T m and m the monomial moments of
+// THIS draw: the sample mean of the same uniforms, not the continuous pupil integral.  The draw is shared by every field point of a
+// (state, wavelength), so the weights are computed once per (state, wavelength): chief_fit_weights_kernel, float64, one workgroup
+// each.  Nodes and pinv(V)^T are constants (chief_fit_tables.h, tools/gen_chief_fit_tables.py); two weight vectors, degree d and
+// d - 2 over the same nodes, feed the truncation guard of the PSF kernel.
+// ------------------------------------------------------------------------------------
+constexpr int kChiefNodes = AADFF_CHIEF_NODES, kChiefRays = AADFF_CHIEF_RAYS;
+constexpr int kFitMono = AADFF_CHIEF_FIT_MONOMIALS, kFitMonoLow = AADFF_CHIEF_FIT_MONOMIALS_LOW, kFitDegree = AADFF_CHIEF_DEGREE;
+constexpr int kFitThreads = 512, kFitBatch = 4, kFitSplit = kFitThreads / kChiefNodes, kFitPiece = (kFitMono + kFitSplit - 1) / kFitSplit;
+constexpr int kFitChunk = kFitThreads / 64;
+static_assert(kChiefRays == 128 && kChiefNodes <= kChiefRays && kChiefNodes >= 64, "one wave of 64 lanes x 2 rays; every lane's first ray is a node");
+static_assert(kFitMono == (kFitDegree + 1) * (kFitDegree + 2) / 2 && kFitMonoLow == (kFitDegree - 1) * kFitDegree / 2, "monomials by total degree");
+static_assert(kFitMono <= kFitThreads && 2 * kChiefNodes <= kFitThreads, "chief_fit_weights_kernel: one thread per moment / per weight");
+static const double h_chief_node_xy[kChiefRays * 2] = AADFF_CHIEF_NODE_XY_INIT;
+static const double h_chief_fit[kFitMono * kChiefNodes] = AADFF_CHIEF_FIT_INIT;
+static const double h_chief_fit_low[kFitMonoLow * kChiefNodes] = AADFF_CHIEF_FIT_LOW_INIT;
+__device__ const float d_chief_node_xy[kChiefRays * 2] = AADFF_CHIEF_NODE_XY_INIT;
+__device__ const double d_chief_fit[kFitMono * kChiefNodes] = AADFF_CHIEF_FIT_INIT;
+__device__ const double d_chief_fit_low[kFitMonoLow * kChiefNodes] = AADFF_CHIEF_FIT_LOW_INIT;
+// A fitted centre is taken only where the degree-d and degree-(d - 2) centres agree within this (mm, either axis).  Among the
+// workgroups of the bench configuration whose node and ring rays are all alive the difference is float32 trace noise, 1.2e-7 mm in the
+// median and 2.1e-6 mm at most; 1.3 % of them exceed the tolerance and trace every draw
+constexpr float kChiefFitTol = AADFF_CHIEF_FIT_TOL;
+
+// grid (L, S); u_late: the address u_chief has in the mapped pinned block for states >= late_from (staged launches), else unused
+__global__ __launch_bounds__(kFitThreads) void chief_fit_weights_kernel(const float* __restrict__ u_chief, const float* __restrict__ u_late, int late_from,
+                                                                         int L, int spp_chief, long chief_ss, long chief_sl, float* __restrict__ weights) {
+    __shared__ double buf[kFitChunk][kFitThreads];
+    __shared__ double mom[kFitMono];
+    __shared__ double wsum[kFitSplit][2][kChiefNodes];
+    const int l = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
+    const float* ut = (s >= late_from ? u_late : u_chief) + (size_t)s * chief_ss + (size_t)l * chief_sl;
+    const float* ur = ut + spp_chief;
+    double acc[kFitMono];
+#pragma unroll
+    for (int j = 0; j < kFitMono; ++j) acc[j] = 0.0;
+    for (int i0 = tid; i0 < spp_chief; i0 += kFitBatch * kFitThreads) {
+        float ua[kFitBatch], ub[kFitBatch];              // a batch of loads in flight at once: the draws of a staged launch come over PCIe
+#pragma unroll
+        for (int q = 0; q < kFitBatch; ++q) {
+            const int i = min(i0 + q * kFitThreads, spp_chief - 1);
+            ua[q] = ut[i]; ub[q] = ur[i];
+        }
+#pragma unroll
+        for (int q = 0; q < kFitBatch; ++q) {
+            if (i0 + q * kFitThreads >= spp_chief) break;
+            // the unit-disc point of disc_sample2 (same square root, same sine and cosine), without the pupil radius
+            const float rr = fsqrt(ub[q]), ang = ua[q];
+#ifndef AADFF_LIBM_SINCOS
+            const double x = (double)(rr * __builtin_amdgcn_cosf(ang)), y = (double)(rr * __builtin_amdgcn_sinf(ang));
+#else
+            const double x = (double)(rr * cosf(ang * 2.f * kTwoPiHi)), y = (double)(rr * sinf(ang * 2.f * kTwoPiHi));
+#endif
+            double px[kFitDegree + 1], py[kFitDegree + 1];
+            px[0] = py[0] = 1.0;
+#pragma unroll
+            for (int k = 1; k <= kFitDegree; ++k) { px[k] = px[k - 1] * x; py[k] = py[k - 1] * y; }
+            int j = 0;
+#pragma unroll
+            for (int d = 0; d <= kFitDegree; ++d)
+#pragma unroll
+                for (int b = 0; b <= d; ++b) acc[j++] += px[d - b] * py[b];
+        }
+    }
+    // sums over the threads, kFitChunk moments at a time through LDS: a wave per moment adds the waves' partial sums lane by lane
+    // and finishes with one shuffle tree (a shuffle tree per moment and wave is 66 x 6 LDS permutes of doubles, one after the other)
+#pragma unroll
+    for (int c = 0; c < kFitMono; c += kFitChunk) {
+#pragma unroll
+        for (int q = 0; q < kFitChunk; ++q)
+            if (c + q < kFitMono) buf[q][tid] = acc[c + q];
+        __syncthreads();
+        const int m = tid >> 6, sub = tid & 63;
+        double v = 0.0;
+#pragma unroll
+        for (int e = 0; e < kFitThreads / 64; ++e) v += buf[m][sub + 64 * e];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+        if (sub == 0 && c + m < kFitMono) mom[c + m] = v / (double)spp_chief;
+        __syncthreads();
+    }
+    // w = pinv(V)^T m: the rows of a node split over kFitSplit threads (a thread alone waits for 111 loads one after the other)
+    const int k = tid % kChiefNodes, piece = tid / kChiefNodes;
+    if (piece < kFitSplit) {
+        double w = 0.0, wl = 0.0;
+#pragma unroll
+        for (int q = 0; q < kFitPiece; ++q) {
+            const int j = piece * kFitPiece + q;
+            if (j < kFitMono) w += d_chief_fit[j * kChiefNodes + k] * mom[j];
+            if (j < kFitMonoLow) wl += d_chief_fit_low[j * kChiefNodes + k] * mom[j];
+        }
+        wsum[piece][0][k] = w; wsum[piece][1][k] = wl;
+    }
+    __syncthreads();
+    if (tid < 2 * kChiefNodes) {
+        const int which = tid / kChiefNodes;
+        double w = 0.0;
+#pragma unroll
+        for (int q = 0; q < kFitSplit; ++q) w += wsum[q][which][k];
+        weights[(size_t)(s * L + l) * 2 * kChiefNodes + tid] = (float)w;
+    }
+}
+
+// ------------------------------------------------------------------------------------
 // generic kernels
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void trace_rays_kernel(const float* o_in, const float* d_in, const float* ra_in,
@@ -994,7 +1101,8 @@ __device__ __forceinline__ PsfLds psf_lds() {
 #endif
 }
 
-template <bool EDGE, class SEQ>
+// FIT: the launch carries fitted chief centres (fit_c); without it the body is the code of a launch that never had any
+template <bool EDGE, class SEQ, bool FIT = false>
 __device__ __forceinline__ void psf_points_body(const PsfLds& lds, const float* __restrict__ points, int N, int L,
                                                           const aadff_surface_t* __restrict__ surf_main,
                                                           const aadff_surface_t* __restrict__ surf_chief,
@@ -1003,7 +1111,8 @@ __device__ __forceinline__ void psf_points_body(const PsfLds& lds, const float* 
                                                           const float* __restrict__ u_main, int spp, long main_ss,
                                                           long main_sl, const float* __restrict__ u_chief,
                                                           int spp_chief, long chief_ss, long chief_sl, SplatGeom g, int centre_mode, int map_grid, float* psf,
-                                                          float* centre_out, int* flags, StageArgs stage, const EdgeArgs& edge) {
+                                                          float* centre_out, int* flags, StageArgs stage, const EdgeArgs& edge,
+                                                          const float* __restrict__ fit_c = nullptr) {
     extern __shared__ float hist[];                      // ks * ks floats (dynamic: ks up to AADFF_MAX_KS = 51)
     float* const red = lds.red;
     int& stage_late = *lds.stage_late;
@@ -1077,8 +1186,13 @@ __device__ __forceinline__ void psf_points_body(const PsfLds& lds, const float* 
         const float* ur = ut + spp_chief;
         float sx = 0.f, sy = 0.f, sw = 0.f;
         [[maybe_unused]] float tx = 0.f, ty = 0.f;       // EDGE: sums of the direction tangents of the valid chief rays
+        // fit launches: chief_fit_centres_kernel has left {hit x, hit y, guards passed, -} for every workgroup;
+        // where the guards passed the centre stands and no chief ray is traced here, elsewhere every draw is, as without a fit
+        const float* fc = FIT && !EDGE && fit_c ? fit_c + ((size_t)(s * L + l) * N + n) * 4 : nullptr;
+        const bool fitted = fc && fc[2] != 0.f;          // workgroup-uniform
+        const int n_chief = fitted ? 0 : spp_chief;
 #ifndef AADFF_PSF_SCALAR
-        for (int i = tid; i < spp_chief; i += 2 * kPsfThreads) {
+        for (int i = tid; i < n_chief; i += 2 * kPsfThreads) {
             const int i1 = i + kPsfThreads;
             const i2 act = {-1, i1 < spp_chief ? -1 : 0};
             const int j1 = act.y ? i1 : i;
@@ -1096,7 +1210,7 @@ __device__ __forceinline__ void psf_points_body(const PsfLds& lds, const float* 
             }
         }
 #else
-        for (int i = tid; i < spp_chief; i += kPsfThreads) {
+        for (int i = tid; i < n_chief; i += kPsfThreads) {
             float x2, y2;
             disc_sample(ut[i], ur[i], lc.enp_r2_shrunk, x2, y2);
             Ray r = ray_to(px, py, depth, x2, y2, lc.enp_z);
@@ -1105,25 +1219,30 @@ __device__ __forceinline__ void psf_points_body(const PsfLds& lds, const float* 
             sx += r.ox * r.ra; sy += r.oy * r.ra; sw += r.ra;
         }
 #endif
-        sx = wave_sum(sx); sy = wave_sum(sy); sw = wave_sum(sw);
-        if (EDGE) { tx = wave_sum(tx); ty = wave_sum(ty); }
-        if ((tid & 63) == 0) {
-            red[(tid >> 6) * 3] = sx; red[(tid >> 6) * 3 + 1] = sy; red[(tid >> 6) * 3 + 2] = sw;
-            if (EDGE) { red[3 * kPsfWaves + (tid >> 6) * 2] = tx; red[3 * kPsfWaves + (tid >> 6) * 2 + 1] = ty; }
-        }
-        __syncthreads();
-        sx = sy = sw = 0.f;
+        if (fitted) {
+            cx = -fc[0]; cy = -fc[1];
+            __syncthreads();
+        } else {
+            sx = wave_sum(sx); sy = wave_sum(sy); sw = wave_sum(sw);
+            if (EDGE) { tx = wave_sum(tx); ty = wave_sum(ty); }
+            if ((tid & 63) == 0) {
+                red[(tid >> 6) * 3] = sx; red[(tid >> 6) * 3 + 1] = sy; red[(tid >> 6) * 3 + 2] = sw;
+                if (EDGE) { red[3 * kPsfWaves + (tid >> 6) * 2] = tx; red[3 * kPsfWaves + (tid >> 6) * 2 + 1] = ty; }
+            }
+            __syncthreads();
+            sx = sy = sw = 0.f;
 #pragma unroll
-        for (int w = 0; w < kPsfWaves; ++w) { sx += red[3 * w]; sy += red[3 * w + 1]; sw += red[3 * w + 2]; }
-        cx = -(sx / (sw + kEps));
-        cy = -(sy / (sw + kEps));
-        if (EDGE && edge.slope && tid == 0) {
-            tx = ty = 0.f;
-            for (int w = 0; w < kPsfWaves; ++w) { tx += red[3 * kPsfWaves + 2 * w]; ty += red[3 * kPsfWaves + 2 * w + 1]; }
-            float* so = edge.slope + ((size_t)(s * L + l) * N + n) * 2;
-            so[0] = tx / (sw + kEps); so[1] = ty / (sw + kEps);
+            for (int w = 0; w < kPsfWaves; ++w) { sx += red[3 * w]; sy += red[3 * w + 1]; sw += red[3 * w + 2]; }
+            cx = -(sx / (sw + kEps));
+            cy = -(sy / (sw + kEps));
+            if (EDGE && edge.slope && tid == 0) {
+                tx = ty = 0.f;
+                for (int w = 0; w < kPsfWaves; ++w) { tx += red[3 * kPsfWaves + 2 * w]; ty += red[3 * kPsfWaves + 2 * w + 1]; }
+                float* so = edge.slope + ((size_t)(s * L + l) * N + n) * 2;
+                so[0] = tx / (sw + kEps); so[1] = ty / (sw + kEps);
+            }
+            if (sw == 0.f && tid == 0 && flags) atomicOr(flags, 2);      // "No sampled rays is valid." (optics.py:901)
         }
-        if (sw == 0.f && tid == 0 && flags) atomicOr(flags, 2);      // "No sampled rays is valid." (optics.py:901)
     } else {
         cx = xn * (lc.sensor_w / 2.f);                               // optics.py:972-974
         cy = yn * (lc.sensor_h / 2.f);
@@ -1237,10 +1356,66 @@ __device__ __forceinline__ void psf_points_body(const PsfLds& lds, const float* 
     if (nan_flag && flags) atomicOr(flags, 1);
 }
 
+// Chief-centre fit, the node rays: one wave per (point, wavelength, state) traces the kChiefRays node and guard-ring rays of the shrunk
+// pupil, lane i the rays i and i + 64, through the PSF kernel's own trace_pair_to_sensor, and leaves {hit x, hit y, ok, 0} in
+// out [S][L][N][4].  The hit is h_0 + sum_k w_k (h_k - h_0) with h_0 the centre node's (an error in sum w then multiplies a spot size,
+// not a sensor coordinate); ok unless a node or ring ray died (vignetting reaches into the shrunk pupil: the hit is no polynomial
+// there) or the degree-d and degree-(d - 2) hits disagree.  A kernel of its own, not a first pass of the PSF kernel's workgroups: there
+// one wave traced while seven waited, the workgroup kept its LDS and wave slots meanwhile, and of the 45 % of the instructions saved
+// for three workgroups in five the kernel got 5 % faster.
+constexpr int kNodeWaves = 4;
+template <class SEQ>
+__device__ __forceinline__ void chief_fit_centre_body(const float* __restrict__ points, int N, int L, const aadff_surface_t* __restrict__ surf_chief,
+                                                      aadff_lens_const_t lc, const aadff_lens_state_t* __restrict__ states,
+                                                      const float* __restrict__ fit_w, float* __restrict__ out, int n, int l, int s) {
+    const int i = threadIdx.x & 63, j1 = i + 64;
+    const float d_sensor = fresh_uniform(&states[s].d_sensor), tan_hfov = fresh_uniform(&states[s].tan_hfov);
+    const float* pt = points + ((size_t)s * N + n) * 3;
+    const float xn = pt[0], yn = pt[1], depth = pt[2];
+    const float scale = (-depth) * tan_hfov / lc.r_last;            // as psf_points_body
+    const float px = xn * scale * lc.sensor_w / 2.f;
+    const float py = yn * scale * lc.sensor_h / 2.f;
+    const float rs = fsqrt(lc.enp_r2_shrunk);
+    const f2 x2 = (f2){d_chief_node_xy[2 * i], d_chief_node_xy[2 * j1]} * rs, y2 = (f2){d_chief_node_xy[2 * i + 1], d_chief_node_xy[2 * j1 + 1]} * rs;
+    int nan_flag = 0;                                               // a NaN in a ray that is not one of the reference's is no error of the reference's
+    const Ray2 r = trace_pair_to_sensor<SEQ>(px, py, depth, x2, y2, lc.enp_z, (i2){-1, -1}, surf_chief, lc.n_surf, d_sensor, nan_flag);
+    const float* w = fit_w + (size_t)(s * L + l) * 2 * kChiefNodes;
+    const float hx0 = __shfl(r.ox.x, 0, kWave), hy0 = __shfl(r.oy.x, 0, kWave);
+    const bool node1 = j1 < kChiefNodes;                            // i < 64 <= kChiefNodes: a lane's first ray always is a node
+    const f2 wd = {w[i], node1 ? w[j1] : 0.f}, wl = {w[kChiefNodes + i], node1 ? w[kChiefNodes + j1] : 0.f};
+    const f2 ex = r.ox - hx0, ey = r.oy - hy0;
+    const f2 adx = wd * ex, ady = wd * ey, alx = wl * ex, aly = wl * ey;
+    const float fx = wave_sum(adx.x + adx.y), fy = wave_sum(ady.x + ady.y);
+    const float gx = wave_sum(alx.x + alx.y), gy = wave_sum(aly.x + aly.y);
+    const bool all_alive = __all(r.alive.x != 0 && r.alive.y != 0);
+    if (i == 0) {
+        const bool ok = all_alive && fabsf(fx - gx) <= kChiefFitTol && fabsf(fy - gy) <= kChiefFitTol;
+        *reinterpret_cast<float4*>(out + ((size_t)(s * L + l) * N + n) * 4) = make_float4(hx0 + fx, hy0 + fy, ok ? 1.f : 0.f, 0.f);
+    }
+}
+// grid (ceil(N / kNodeWaves), L, S); surf_main: the table whose kinds decide the trace with surf_chief's, as in psf_points_dispatch
+__global__ __launch_bounds__(kNodeWaves * 64) void chief_fit_centres_kernel(const float* __restrict__ points, int N, int L,
+                                                                             const aadff_surface_t* __restrict__ surf_main,
+                                                                             const aadff_surface_t* __restrict__ surf_chief, aadff_lens_const_t lc,
+                                                                             const aadff_lens_state_t* __restrict__ states,
+                                                                             const float* __restrict__ fit_w, int trace_mode, float* __restrict__ out) {
+    const int n = blockIdx.x * kNodeWaves + (threadIdx.x >> 6), l = blockIdx.y, s = blockIdx.z;
+    if (n >= N) return;                                             // whole waves
+    auto body = [&](auto seq) { chief_fit_centre_body<decltype(seq)>(points, N, L, surf_chief, lc, states, fit_w, out, n, l, s); };
+    [[maybe_unused]] const int path = psf_seq_path(surf_main + (size_t)l * lc.n_surf, surf_chief, lc.n_surf, trace_mode == 1);
+#ifndef AADFF_PSF_NO_SEQ
+    if (path == 1) body(seq::Rf50mm{});
+    else if (path == 2) body(seq::F28{});
+    else
+#endif
+        body(KindLoop{});
+}
+
 // One body per kind sequence, chosen once per workgroup.  The kinds are the same in every wavelength's table (only the indices
 // differ); this workgroup's own is the one checked, and the chief table where the chief pass runs.  trace_mode (AADFF_PSF_TRACE):
 // 1 = the loop for every lens; 2 = as 0, and a workgroup that takes a compiled sequence ORs kPsfSeqFlag << (path - 1) into flags.
 constexpr int kPsfSeqFlag = 256;
+template <bool FIT>
 __device__ __forceinline__ void psf_points_dispatch(const float* __restrict__ points, int N, int L,
                                                     const aadff_surface_t* __restrict__ surf_main,
                                                     const aadff_surface_t* __restrict__ surf_chief,
@@ -1249,11 +1424,11 @@ __device__ __forceinline__ void psf_points_dispatch(const float* __restrict__ po
                                                     const float* __restrict__ u_main, int spp, long main_ss,
                                                     long main_sl, const float* __restrict__ u_chief,
                                                     int spp_chief, long chief_ss, long chief_sl, SplatGeom g, int centre_mode, int map_grid, float* psf,
-                                                    float* centre_out, int* flags, StageArgs stage, int trace_mode) {
+                                                    float* centre_out, int* flags, StageArgs stage, int trace_mode, const float* __restrict__ fit_c) {
     const PsfLds lds = psf_lds<false>();
     auto body = [&](auto seq) {
-        psf_points_body<false, decltype(seq)>(lds, points, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_ss, main_sl, u_chief, spp_chief, chief_ss,
-                                              chief_sl, g, centre_mode, map_grid, psf, centre_out, flags, stage, EdgeArgs{});
+        psf_points_body<false, decltype(seq), FIT>(lds, points, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_ss, main_sl, u_chief, spp_chief, chief_ss,
+                                              chief_sl, g, centre_mode, map_grid, psf, centre_out, flags, stage, EdgeArgs{}, fit_c);
     };
     [[maybe_unused]] const int path = psf_seq_path(surf_main + (size_t)blockIdx.y * lc.n_surf, centre_mode == 1 ? surf_chief : nullptr, lc.n_surf, trace_mode == 1);
 #ifndef AADFF_PSF_NO_SEQ
@@ -1266,7 +1441,7 @@ __device__ __forceinline__ void psf_points_dispatch(const float* __restrict__ po
 }
 
 // TIMED: the same code under a second name for the launches that carry aadff_time_next_launch's events (see conv.hip)
-template <bool TIMED>
+template <bool TIMED, bool FIT>
 __global__ __launch_bounds__(kPsfThreads, 6) void psf_points_kernel(const float* __restrict__ points, int N, int L,
                                                           const aadff_surface_t* __restrict__ surf_main,
                                                           const aadff_surface_t* __restrict__ surf_chief,
@@ -1275,9 +1450,9 @@ __global__ __launch_bounds__(kPsfThreads, 6) void psf_points_kernel(const float*
                                                           const float* __restrict__ u_main, int spp, long main_ss,
                                                           long main_sl, const float* __restrict__ u_chief,
                                                           int spp_chief, long chief_ss, long chief_sl, SplatGeom g, int centre_mode, int map_grid, float* psf,
-                                                          float* centre_out, int* flags, StageArgs stage, int trace_mode) {
-    psf_points_dispatch(points, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_ss, main_sl, u_chief, spp_chief, chief_ss, chief_sl, g,
-                        centre_mode, map_grid, psf, centre_out, flags, stage, trace_mode);
+                                                          float* centre_out, int* flags, StageArgs stage, int trace_mode, const float* __restrict__ fit_c) {
+    psf_points_dispatch<FIT>(points, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_ss, main_sl, u_chief, spp_chief, chief_ss, chief_sl, g,
+                        centre_mode, map_grid, psf, centre_out, flags, stage, trace_mode, fit_c);
 }
 
 // the edge-exact form: band rays deferred to aadff_strict_edge_retrace, histograms left unnormalised in edge.raw.  It stays on the
@@ -2003,12 +2178,18 @@ static int psf_trace_mode() {
     return !e ? 0 : strcmp(e, "loop") == 0 ? 1 : strcmp(e, "mark") == 0 ? 2 : 0;
 }
 
+// AADFF_PSF_CHIEF, read per launch: "full" makes a fit launch a launch without weights - every chief centre from every draw
+static bool psf_chief_full() {
+    const char* e = getenv("AADFF_PSF_CHIEF");
+    return e && strcmp(e, "full") == 0;
+}
+
 static int psf_points_launch(const float* points, int S, int N, int L, const aadff_surface_t* surf_main,
                      const aadff_surface_t* surf_chief, aadff_lens_const_t lc, const aadff_lens_state_t* states,
                      const float* u_main, int spp, long main_stride_s, long main_stride_l, const float* u_chief,
                      int spp_chief, long chief_stride_s, long chief_stride_l, int ks, int centre_mode,
                      int map_layout, float* psf, float* centre_out_or_null, int* flags_or_null,
-                     const aadff_stage_t* stage, aadff_stream_t stream) {
+                     const aadff_stage_t* stage, const float* fit_weights, float* fit_centres, aadff_stream_t stream) {
     AADFF_CHECK_ARG(points && surf_main && states && u_main && psf, "psf_points: NULL pointer");
     AADFF_CHECK_ARG(centre_mode == 0 || (surf_chief && u_chief && spp_chief > 0), "psf_points: chief-ray centre needs surf_chief/u_chief");
     AADFF_CHECK_ARG(S > 0 && S <= 65535 && N > 0 && L > 0 && L <= 65535 && spp > 0, "psf_points: bad sizes S=%d N=%d L=%d spp=%d", S, N, L, spp);
@@ -2045,18 +2226,29 @@ static int psf_points_launch(const float* points, int S, int N, int L, const aad
                         "psf_points_staged: u_main/u_chief must point into dst_dev[0 .. S*slice_stride)");
     }
     const int trace_mode = psf_trace_mode();
+    const float* fit_c = nullptr;
+    if (fit_weights && centre_mode == 1 && spp_chief >= 4 * kChiefRays && !psf_chief_full()) {
+        AADFF_CHECK_ARG(fit_centres, "psf_points_fit: fit_weights without fit_centres");
+        hipLaunchKernelGGL(chief_fit_centres_kernel, dim3((N + kNodeWaves - 1) / kNodeWaves, L, S), dim3(kNodeWaves * 64), 0, (hipStream_t)stream, points, N, L,
+                           surf_main, surf_chief, lc, states, fit_weights, trace_mode, fit_centres);
+        AADFF_CHECK_LAUNCH();
+        fit_c = fit_centres;
+    }
     hipEvent_t ev0 = g_time_start, ev1 = g_time_stop;                    // aadff_time_next_launch
     g_time_start = g_time_stop = nullptr;
+    // four instances of one kernel: with or without the events of aadff_time_next_launch, with or without fitted centres
+    const auto kern = fit_c ? (ev0 ? psf_points_kernel<true, true> : psf_points_kernel<false, true>)
+                            : (ev0 ? psf_points_kernel<true, false> : psf_points_kernel<false, false>);
     if (ev0)
-        hipExtLaunchKernelGGL(psf_points_kernel<true>, dim3(N, L, sa.src ? S + 1 : S), dim3(kPsfThreads), (size_t)ks * ks * sizeof(float), (hipStream_t)stream,
+        hipExtLaunchKernelGGL(kern, dim3(N, L, sa.src ? S + 1 : S), dim3(kPsfThreads), (size_t)ks * ks * sizeof(float), (hipStream_t)stream,
                               ev0, ev1, 0, points, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_stride_s, main_stride_l, u_chief,
                               spp_chief, chief_stride_s, chief_stride_l, make_splat_geom(lc.pixel_size, ks), centre_mode, map_grid, psf,
-                              centre_out_or_null, flags_or_null, sa, trace_mode);
+                              centre_out_or_null, flags_or_null, sa, trace_mode, fit_c);
     else
-        hipLaunchKernelGGL(psf_points_kernel<false>, dim3(N, L, sa.src ? S + 1 : S), dim3(kPsfThreads), (size_t)ks * ks * sizeof(float), (hipStream_t)stream, points, N, L, surf_main,
+        hipLaunchKernelGGL(kern, dim3(N, L, sa.src ? S + 1 : S), dim3(kPsfThreads), (size_t)ks * ks * sizeof(float), (hipStream_t)stream, points, N, L, surf_main,
                            surf_chief, lc, states, u_main, spp, main_stride_s, main_stride_l, u_chief, spp_chief, chief_stride_s,
                            chief_stride_l, make_splat_geom(lc.pixel_size, ks),
-                           centre_mode, map_grid, psf, centre_out_or_null, flags_or_null, sa, trace_mode);
+                           centre_mode, map_grid, psf, centre_out_or_null, flags_or_null, sa, trace_mode, fit_c);
     AADFF_CHECK_LAUNCH();
     return 0;
 }
@@ -2069,7 +2261,18 @@ int aadff_psf_points(const float* points, int S, int N, int L, const aadff_surfa
                      aadff_stream_t stream) {
     return psf_points_launch(points, S, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_stride_s, main_stride_l,
                              u_chief, spp_chief, chief_stride_s, chief_stride_l, ks, centre_mode, map_layout, psf,
-                             centre_out_or_null, flags_or_null, nullptr, stream);
+                             centre_out_or_null, flags_or_null, nullptr, nullptr, nullptr, stream);
+}
+
+int aadff_psf_points_fit(const float* points, int S, int N, int L, const aadff_surface_t* surf_main,
+                         const aadff_surface_t* surf_chief, aadff_lens_const_t lc, const aadff_lens_state_t* states,
+                         const float* u_main, int spp, long main_stride_s, long main_stride_l, const float* u_chief,
+                         int spp_chief, long chief_stride_s, long chief_stride_l, int ks, int centre_mode,
+                         int map_layout, float* psf, float* centre_out_or_null, int* flags_or_null,
+                         const float* fit_weights_or_null, float* fit_centres, aadff_stream_t stream) {
+    return psf_points_launch(points, S, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_stride_s, main_stride_l,
+                             u_chief, spp_chief, chief_stride_s, chief_stride_l, ks, centre_mode, map_layout, psf,
+                             centre_out_or_null, flags_or_null, nullptr, fit_weights_or_null, fit_centres, stream);
 }
 
 int aadff_psf_points_staged(const float* points, int S, int N, int L, const aadff_surface_t* surf_main,
@@ -2081,7 +2284,54 @@ int aadff_psf_points_staged(const float* points, int S, int N, int L, const aadf
     AADFF_CHECK_ARG(stage, "psf_points_staged: NULL stage");
     return psf_points_launch(points, S, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_stride_s, main_stride_l,
                              u_chief, spp_chief, chief_stride_s, chief_stride_l, ks, centre_mode, map_layout, psf,
-                             centre_out_or_null, flags_or_null, stage, stream);
+                             centre_out_or_null, flags_or_null, stage, nullptr, nullptr, stream);
+}
+
+int aadff_psf_points_staged_fit(const float* points, int S, int N, int L, const aadff_surface_t* surf_main,
+                                const aadff_surface_t* surf_chief, aadff_lens_const_t lc, const aadff_lens_state_t* states,
+                                const float* u_main, int spp, long main_stride_s, long main_stride_l, const float* u_chief,
+                                int spp_chief, long chief_stride_s, long chief_stride_l, int ks, int centre_mode,
+                                int map_layout, float* psf, float* centre_out_or_null, int* flags_or_null,
+                                const aadff_stage_t* stage, const float* fit_weights_or_null, float* fit_centres, aadff_stream_t stream) {
+    AADFF_CHECK_ARG(stage, "psf_points_staged_fit: NULL stage");
+    return psf_points_launch(points, S, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_stride_s, main_stride_l,
+                             u_chief, spp_chief, chief_stride_s, chief_stride_l, ks, centre_mode, map_layout, psf,
+                             centre_out_or_null, flags_or_null, stage, fit_weights_or_null, fit_centres, stream);
+}
+
+int aadff_chief_fit_weights(const float* u_chief, int S, int L, int spp_chief, long chief_stride_s, long chief_stride_l,
+                            const aadff_stage_t* stage_or_null, float* weights, aadff_stream_t stream) {
+    AADFF_CHECK_ARG(u_chief && weights, "chief_fit_weights: NULL pointer");
+    AADFF_CHECK_ARG(S > 0 && S <= 65535 && L > 0 && L <= 65535 && spp_chief > 0, "chief_fit_weights: bad sizes S=%d L=%d spp_chief=%d", S, L, spp_chief);
+    const float* u_late = u_chief;
+    int late_from = S;
+    if (stage_or_null && stage_or_null->first_slice < S) {
+        // the draws of the states >= first_slice are still on the host when this kernel runs: read them where the late path of the
+        // PSF launch does, at u_chief's place in the mapped pinned block
+        const aadff_stage_t* stage = stage_or_null;
+        AADFF_CHECK_ARG(stage->src_host && stage->dst_dev && stage->first_slice >= 0 && stage->slice_stride > 0, "chief_fit_weights: bad aadff_stage_t");
+        AADFF_CHECK_ARG(u_chief >= stage->dst_dev && u_chief < stage->dst_dev + (long)S * stage->slice_stride,
+                        "chief_fit_weights: u_chief must point into dst_dev[0 .. S*slice_stride)");
+        void* mapped = nullptr;
+        if (hipHostGetDevicePointer(&mapped, const_cast<float*>(stage->src_host), 0) != hipSuccess || !mapped) {
+            (void)hipGetLastError();
+            AADFF_CHECK_ARG(false, "chief_fit_weights: src_host is not pinned (device-mapped) host memory");
+        }
+        u_late = reinterpret_cast<const float*>(mapped) + (u_chief - stage->dst_dev);
+        late_from = stage->first_slice;
+    }
+    hipLaunchKernelGGL(chief_fit_weights_kernel, dim3(L, S), dim3(kFitThreads), 0, (hipStream_t)stream, u_chief, u_late, late_from, L, spp_chief,
+                       chief_stride_s, chief_stride_l, weights);
+    AADFF_CHECK_LAUNCH();
+    return 0;
+}
+
+int aadff_chief_fit_tables(double* node_xy, double* fit, double* fit_low) {
+    AADFF_CHECK_ARG(node_xy && fit && fit_low, "chief_fit_tables: NULL pointer");
+    std::memcpy(node_xy, h_chief_node_xy, sizeof(h_chief_node_xy));
+    std::memcpy(fit, h_chief_fit, sizeof(h_chief_fit));
+    std::memcpy(fit_low, h_chief_fit_low, sizeof(h_chief_fit_low));
+    return 0;
 }
 
 int aadff_psf_points_edge(const float* points, int S, int N, int L, const aadff_surface_t* surf_main,

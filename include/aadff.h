@@ -657,6 +657,45 @@ int aadff_psf_points_staged(const float* points, int S, int N, int L,
                      int ks, int centre_mode, int map_layout, float* psf, float* centre_out_or_null,
                      int* flags_or_null, const aadff_stage_t* stage, aadff_stream_t stream);
 
+/* Chief-centre fit.  Where no chief ray of a point is vignetted, the sensor hit is a smooth function of the pupil position, and the
+ * chief centre - its mean over the spp_chief draws - equals sum_k w_k hit(node_k) over AADFF_CHIEF_NODES fixed nodes of the shrunk
+ * pupil, with weights that follow from the monomial moments of the SAME draws (not the continuous pupil integral: the result is this
+ * draw's sample mean up to the truncation of a degree-AADFF_CHIEF_DEGREE fit).  The draws are shared by all points of a (state,
+ * wavelength), so the weights are computed once per launch:
+ *   aadff_chief_fit_weights: weights [S][L][2][AADFF_CHIEF_NODES] (degree d, then degree d - 2) from the u_chief block the PSF launch
+ *     will read (same pointer and strides).  stage_or_null: the aadff_stage_t of the staged PSF launch that follows on the same
+ *     stream - the draws of states >= first_slice are then read from the pinned host block, where they still are.
+ *   aadff_psf_points_fit / aadff_psf_points_staged_fit: aadff_psf_points / _staged with that buffer and fit_centres, scratch of
+ *     [S][L][N][4] floats (16-byte aligned).  With centre_mode 1 and spp_chief >= 4 * AADFF_CHIEF_RAYS, a launch of one wave per
+ *     (point, wavelength, state) in front of the PSF launch traces the nodes and a guard ring at 1.05 x the shrunk-pupil radius
+ *     (AADFF_CHIEF_RAYS rays in all); the fitted centre stands if every one of those rays is alive and the degree-d and
+ *     degree-(d - 2) centres agree; otherwise the PSF workgroup traces every draw, as without weights and with the same bits.
+ *     fit_weights_or_null = NULL, or AADFF_PSF_CHIEF=full in the environment (read per launch), is aadff_psf_points / _staged.
+ *   aadff_chief_fit_tables (host only, for tests): node_xy [AADFF_CHIEF_RAYS][2] in the unit disc (nodes, centre first, then the
+ *     ring); fit [66][AADFF_CHIEF_NODES] and fit_low [45][AADFF_CHIEF_NODES]: pinv(V)^T of the monomial bases of total degree d and
+ *     d - 2 (x^(t-b) y^b, ordered by t then b), transposed.  tools/gen_chief_fit_tables.py generates them. */
+#define AADFF_CHIEF_NODES 85
+#define AADFF_CHIEF_RAYS 128
+#define AADFF_CHIEF_DEGREE 10
+#define AADFF_CHIEF_FIT_TOL 1e-6f     /* mm, either axis: the largest |centre_d - centre_(d-2)| a fitted centre may have */
+int aadff_chief_fit_weights(const float* u_chief, int S, int L, int spp_chief, long chief_stride_s, long chief_stride_l,
+                            const aadff_stage_t* stage_or_null, float* weights, aadff_stream_t stream);
+int aadff_psf_points_fit(const float* points, int S, int N, int L,
+                     const aadff_surface_t* surf_main, const aadff_surface_t* surf_chief,
+                     aadff_lens_const_t lc, const aadff_lens_state_t* states,
+                     const float* u_main, int spp, long main_stride_s, long main_stride_l,
+                     const float* u_chief, int spp_chief, long chief_stride_s, long chief_stride_l,
+                     int ks, int centre_mode, int map_layout, float* psf, float* centre_out_or_null,
+                     int* flags_or_null, const float* fit_weights_or_null, float* fit_centres, aadff_stream_t stream);
+int aadff_psf_points_staged_fit(const float* points, int S, int N, int L,
+                     const aadff_surface_t* surf_main, const aadff_surface_t* surf_chief,
+                     aadff_lens_const_t lc, const aadff_lens_state_t* states,
+                     const float* u_main, int spp, long main_stride_s, long main_stride_l,
+                     const float* u_chief, int spp_chief, long chief_stride_s, long chief_stride_l,
+                     int ks, int centre_mode, int map_layout, float* psf, float* centre_out_or_null,
+                     int* flags_or_null, const aadff_stage_t* stage, const float* fit_weights_or_null, float* fit_centres, aadff_stream_t stream);
+int aadff_chief_fit_tables(double* node_xy, double* fit, double* fit_low);
+
 /* "Edge-exact" PSF grid (ABI v8; Lensgroup(parity="edge")): aadff_psf_points with the one decision the float32 noise of a trace
  * can flip taken out of the fast kernel.  The histogram's only discontinuity is the window test of deeplens/monte_carlo.py:37
  * (`|s| < R - 0.01 ps`): a hit within the noise of that edge lands inside or outside depending on the last bit of the trace
