@@ -11,7 +11,7 @@ The geometric OTF of an object point is the Fourier transform of its spot: with 
     OTF(nu, e) = (1/n) sum_k exp(-2 pi i nu e.(h_k - c)),        MTF = |OTF|,
 
 for a frequency nu (cycles/mm) along a unit vector e.  It is computed here from the traced rays themselves, in one fused HIP launch
-(csrc/trace.hip, `aadff_mtf_points`): no histogram, so no bin width and no window cut-off.  Behind the last surface a ray is a straight
+(csrc/lens_analysis.hip, `aadff_mtf_points`): no histogram, so no bin width and no window cut-off.  Behind the last surface a ray is a straight
 line, so the same rays give the OTF on every sensor plane d_sensor + delta at one multiply-add each - the through-focus curve whose
 peak `aadff.dfocus.depth_from_stack` looks for.  The centre c is subtracted before the multiplication by nu: the hits sit at up to
 +-20 mm and nu reaches hundreds of cycles/mm, float32 phases of the raw positions would be useless.

@@ -9,7 +9,7 @@
 
 Every pixel of the sensor sends `spp` rays per colour channel through stratified points of the exit pupil, backwards through
 all surfaces to the object plane z = depth, and averages the bilinear samples of the scene where they land - one fused HIP
-launch (csrc/trace.hip, `aadff_render_raytraced`) that shares the trace core of the PSF kernels.  No patch seams, no kernel-size
+launch (csrc/render_rt.hip, `aadff_render_raytraced`) that shares the trace core of the PSF kernels.  No patch seams, no kernel-size
 cut-off; distortion, lateral colour and (with `vignetting=True`) the lens's fall-off are in the picture.  The scene is sampled
 so that an ideal lens of magnification -1 / scale renders the identity: nothing is left for the caller to flip.
 

@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Hash the device code of every kernel of csrc/, to show that a move of source text changed no instruction.
 
-  kernel_hash.py emit CSRC_DIR OUT.json     compile every .hip unit of CSRC_DIR to gfx950 assembly with the flags its Makefile
-                                            gives the unit's object, hash every function body -> {symbol: [unit, sha256]}
+  kernel_hash.py emit CSRC_DIR OUT.json [SUFFIX]
+                                            compile every .hip unit of CSRC_DIR to gfx950 assembly with the flags its Makefile
+                                            gives the unit's object, hash every function body -> {symbol: [unit, sha256]}.
+                                            With SUFFIX (_literal, _latestage, _texp1): the objects of libaadffSUFFIX.so, i.e.
+                                            UNIT_SUFFIX.o for the units that library builds as a variant and UNIT.o for the rest
   kernel_hash.py compare OLD.json NEW.json  markdown table: symbol, old hash, new hash, same / different / only in one
 
 A body is the text between the symbol's label and its .Lfunc_end, plus its .amdhsa_kernel descriptor (registers, LDS), with
@@ -20,7 +23,8 @@ import tempfile
 
 
 def unit_asm(csrc, unit, tmp):
-    """assembly of one unit: the Makefile's own compile command for unit.o, turned into a device-only -S run"""
+    """assembly of one object (a unit's name, with the variant's suffix if any): the Makefile's own compile command for unit.o,
+    turned into a device-only -S run"""
     cmd = subprocess.check_output(["make", "-C", csrc, "-n", "-B", "--no-print-directory", unit + ".o"], text=True).strip().splitlines()
     cmd = [c for c in cmd if " -c " in c and c.rstrip().endswith(unit + ".o")][-1].split()
     out = os.path.join(tmp, unit + ".s")
@@ -63,12 +67,17 @@ def bodies(asm):
     return res
 
 
-def emit(csrc, out):
+def emit(csrc, out, suffix=""):
     table = {}
+    variant = set()
+    if suffix:                                # the objects on the link line of the variant's library
+        link = subprocess.check_output(["make", "-C", csrc, "-n", "-B", "--no-print-directory", f"libaadff{suffix}.so"], text=True)
+        variant = {w for ln in link.splitlines() if " -shared " in ln for w in ln.split() if w.endswith(suffix + ".o")}
     with tempfile.TemporaryDirectory() as tmp:
         for src in sorted(os.listdir(csrc)):
             if src.endswith(".hip"):
-                for sym, h in bodies(unit_asm(csrc, src[:-4], tmp)).items():
+                obj = src[:-4] + suffix if src[:-4] + suffix + ".o" in variant else src[:-4]
+                for sym, h in bodies(unit_asm(csrc, obj, tmp)).items():
                     table[sym] = [src, h]
     with open(out, "w") as f:
         json.dump(table, f, indent=0, sort_keys=True)
@@ -112,8 +121,8 @@ def compare(old_path, new_path):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) == 4 and sys.argv[1] == "emit":
-        emit(sys.argv[2], sys.argv[3])
+    if len(sys.argv) in (4, 5) and sys.argv[1] == "emit":
+        emit(*sys.argv[2:])
     elif len(sys.argv) == 4 and sys.argv[1] == "compare":
         compare(sys.argv[2], sys.argv[3])
     else:

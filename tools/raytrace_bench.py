@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The ray-traced render (csrc/trace.hip, aadff_render_raytraced) at 1024 x 1024, spp 64, B = 1 and B = 4: ms per render and
+"""The ray-traced render (csrc/render_rt.hip, aadff_render_raytraced) at 1024 x 1024, spp 64, B = 1 and B = 4: ms per render and
 ray-surface steps per second (3 channels x H x W x spp rays x the lens's surfaces, every ray counted as if it lived to the object
 plane - the figure the PSF-grid kernel's ~590 G steps/s is quoted in).
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The layered ray-traced render (csrc/trace.hip, aadff_render_raytraced_layered) at 1024 x 1024, spp 64, for L = 1, 4, 8 planes
+"""The layered ray-traced render (csrc/render_rt.hip, aadff_render_raytraced_layered) at 1024 x 1024, spp 64, for L = 1, 4, 8 planes
 and B = 1, 4 images per launch, against the plane render (aadff_render_raytraced) timed IN THE SAME RUN at the same size: ms per
 render and the ratio layered / plane for the same B.  The scene is examples/raytraced_rgbd_vs_layered_psf.py's - a disc at -600 mm
 over a background slanting from -1500 to -3000 mm - quantised by depth_layers into L planes; the plane render sees the same image at
