@@ -1114,6 +1114,15 @@ class Lensgroup(DeepObj):
         return out[0].mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to("cpu", torch.uint8).numpy()
 
     @torch.no_grad()
+    def render_blended(self, img, depth=DEPTH, grid=7, ks=51, spp=GEO_SPP):
+        """img [B,3,H,W] at this lens' sensor resolution rendered with the PSF map of `depth`, every pixel's PSF interpolated
+        bilinearly between the grid PSFs around it: `psf_map` composed with `aadff.blend.render_psf_map_blend`, the
+        seam-free sibling of `render_single_img(method='psf')`."""
+        from aadff.blend import render_psf_map_blend
+        assert len(img.shape) == 4 and tuple(img.shape[-2:]) == tuple(self.sensor_res), "Input image should be [B, C, H, W] at the sensor resolution"
+        return render_psf_map_blend(img, self.psf_map(depth=depth, grid=grid, ks=ks, spp=spp), grid)
+
+    @torch.no_grad()
     def draw_psf_map(self, grid=7, depth=DEPTH, ks=51, log_scale=False, quater=False, save_name=None):
         """RGB PSF map at `depth`, every field normalised to its own peak, saved as an image (reference:
         optics.py:1773-1803).  The map comes from the fused PSF-grid kernel; the picture is written with matplotlib like the

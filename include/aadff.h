@@ -142,6 +142,23 @@ int aadff_render_psf_map_stack_strided(const float* img, const float* psf_maps, 
 int aadff_render_psf_map_stack_layered(const float* img, const float* psf_maps, const unsigned char* layer_idx, float* out, int B, int C, int S,
                                        int L, int H, int W, int grid, int ks, aadff_stream_t stream);
 
+/* Seam-free PSF-map rendering (no reference counterpart; the space-variant blur of Hirsch et al., "Efficient filter flow", 2010):
+ * every pixel's PSF is the bilinear interpolation of the four grid PSFs whose nodes surround it.  img [B,C,H,W], psf_maps
+ * [S,C,g*ks,g*ks] (tile (i,j) as aadff_render_psf_map reads it), out [B,C,S,H,W]; S = 1 is a single slice.  node_y, node_x: HOST
+ * pointers to g floats each, strictly increasing: the position of grid row i / grid column j in pixel-index units (pixel centres
+ * at integers; nodes may lie outside the image).  For row y: k = clamp(#{i : node_y[i] <= y} - 1, 0, g-2),
+ * fy = clamp((y - node_y[k]) / (node_y[k+1] - node_y[k]), 0, 1) (g == 1: k = 0, fy = 0), so rows beyond the outer nodes take the
+ * outer PSF; columns alike give l, fx.  With R(i,j) = aadff_render_psf(img, tile (i,j) of map s) (flip, reflect padding):
+ *   out[b,c,s,y,x] = (1-fy) [(1-fx) R(k,l) + fx R(k,l+1)] + fy [(1-fx) R(k+1,l) + fx R(k+1,l+1)]
+ * computed in one launch from the maps (no per-pixel PSF tensor).  Plain fp32 FMA chains over the taps, one per corner PSF, blended
+ * last; no atomics, every output written once, bit-reproducible.  All arguments are validated before any HIP call: NULL pointers,
+ * even ks, ks / grid out of range, H or W <= ks/2, sizes too large for one launch, non-finite nodes, and nodes that are not
+ * strictly increasing (the message names the axis and the index) give AADFF_EINVAL.  Odd ks up to AADFF_MAX_KS; unlike the patch
+ * entries, grid may exceed H or W (cells without a pixel launch nothing). */
+int aadff_render_psf_map_blend_stack(const float* img, const float* psf_maps, float* out,
+                                     const float* node_y, const float* node_x,
+                                     int B, int C, int S, int H, int W, int grid, int ks, aadff_stream_t stream);
+
 /* Measurement aid (no reference counterpart): arm the NEXT aadff_render_psf_map_stack (slice-batched kernel: ks 11, S >= 3)
  * or aadff_psf_points / aadff_psf_points_staged call made by this host thread so that its kernel is launched with the two
  * HIP events (hipEvent_t, timing enabled) attached to the dispatch (hipExtLaunchKernelGGL): hipEventElapsedTime then gives
