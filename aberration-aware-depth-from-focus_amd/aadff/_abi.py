@@ -95,6 +95,7 @@ PROTOTYPES = {
     "aadff_render_psf_map_stack_strided": [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _P],
     "aadff_render_psf_map_stack_layered": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "aadff_render_psf_map_blend_stack": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "aadff_render_psf_map_blend_stack_bwd": [_P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "aadff_time_next_launch": [_P, _P],
     "aadff_render_psf": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "aadff_local_psf_render": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -176,6 +177,10 @@ PROTOTYPES = {
     "aadff_host_pupil_points": [_P, _L, _P, _P, _L, _F, _F, _F, _P, _P, _P, _P, _I],
 }
 OTHER_SYMBOLS = ["aadff_abi_version", "aadff_last_error", "aadff_device_info"]
+# name -> argtypes of the entries that return a byte count (size_t; 0 = rejected, aadff_last_error says why)
+SIZE_PROTOTYPES = {
+    "aadff_render_psf_map_blend_stack_bwd_workspace": [_I, _I, _I, _I, _I, _I, _I],
+}
 
 _lib = None
 
@@ -195,6 +200,10 @@ def load_library(path=None):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
+    for name, args in SIZE_PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = args
+        fn.restype = C.c_size_t
     lib.aadff_abi_version.restype = C.c_int
     lib.aadff_last_error.restype = C.c_char_p
     lib.aadff_device_info.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int]

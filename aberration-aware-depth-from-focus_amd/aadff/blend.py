@@ -11,7 +11,8 @@ and jumps at every patch border; this one is continuous, at four FMAs per tap in
     "psf_map"  where `psf_map` traces them: linspace(-0.98, 0.98, grid) of the field, (u + 1) / 2 * n - 0.5     (default)
     "patch"    the centres of the patches of `render_psf_map`: (i + 0.5) / grid * n - 0.5
     (node_y, node_x)   two explicit 1-D tensors of `grid` strictly increasing values
-Pixels beyond the outer nodes take the outer PSF.  Forward only (gradients are not built): tensors that require grad are refused.
+Pixels beyond the outer nodes take the outer PSF.  Forward only: tensors that require grad are refused here; the differentiable twins
+(gradients to the image and the maps, csrc/conv_blend_bwd.hip) are `aadff.diffrender.render_psf_map_blend[_stack]`.
 The functions call the C entry (aadff_render_psf_map_blend_stack) directly, as the planners of aadff/focal_stack.py do; there is no
 torch custom op for it: the set of `torch.ops.aadff` ops is a recorded one (tests/golden/ops_schemas.json).
 """
@@ -51,7 +52,7 @@ def _nodes(nodes, H, W, grid):
 
 def _prep(img, psf_maps, what):
     if (img.requires_grad or psf_maps.requires_grad) and torch.is_grad_enabled():
-        raise RuntimeError(f"{what}: forward-only HIP op, call it under torch.no_grad() or detach the input (gradients of the blended render are not built)")
+        raise RuntimeError(f"{what}: forward-only HIP op, call it under torch.no_grad() or detach the input (the differentiable twin is aadff.diffrender.{what})")
     _abi.require_gpu()
     return img.device if img.is_cuda else torch.device("cuda", torch.cuda.current_device())
 

@@ -21,8 +21,14 @@ dff.factory.get_lens) and its stack form with the same three gradients: the fuse
 re-evaluates every pixel's Gaussian PSF in the kernel (csrc/thinlens.hip, torch.ops.aadff.thinlens_render_stack_diff) - no
 [N,H,W,ks,ks] tensor in either direction.  With them both lens models of dff.factory.get_lens have a differentiable renderer.
 
-Not covered: gradients through the ray tracer and the M1-layered stack.
+`render_psf_map_blend` / `render_psf_map_blend_stack` are the seam-free renders of aadff/blend.py (every pixel's PSF the bilinear blend of
+the four grid PSFs around it) with gradients to the image and the PSF maps from csrc/conv_blend_bwd.hip: the forward is
+the forward-only kernel, bit for bit, the backward calls aadff_render_psf_map_blend_stack_bwd through the C ABI (no torch custom op),
+computes only the gradients autograd asks for and keeps nothing but the two inputs in between.  `grid` and `nodes` get no gradient.
+
+Not covered: gradients through the ray tracer and the M1-layered stack; gradients to the nodes of the blended render.
 """
+import ctypes as C
 import importlib
 
 import numpy as np
@@ -132,6 +138,76 @@ def local_psf_render_high_res(input, psf, patch_size=[320, 480], kernel_size=11)
             j0, j1 = pj * patch_size[1], min((pj + 1) * patch_size[1], W)
             out[:, :, i0:i1, j0:j1] = local_psf_render(input[:, :, i0:i1, j0:j1], psf[:, i0:i1, j0:j1, :, :], kernel_size=kernel_size)
     return out
+
+
+# ---------------------------------------------------------------- blended PSF-map render (aadff/blend.py, csrc/conv_blend_bwd.hip)
+def _host_ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+class _BlendStack(torch.autograd.Function):
+    """x [B,C,H,W], p [S,C,g ks,g ks] float32 contiguous on the GPU -> [B,C,S,H,W]; node_y, node_x float32 [g] on the CPU."""
+
+    @staticmethod
+    def forward(ctx, x, p, node_y, node_x, grid):
+        B, C_, H, W = x.shape
+        S, ks = p.shape[0], p.shape[-1] // grid
+        out = x.new_empty((B, C_, S, H, W))
+        with _abi.on_device(x.device):
+            _abi.call("aadff_render_psf_map_blend_stack", _abi.ptr(x), _abi.ptr(p), _abi.ptr(out), _host_ptr(node_y), _host_ptr(node_x),
+                      B, C_, S, H, W, grid, ks, _abi.stream_ptr(x.device))
+        ctx.save_for_backward(x, p)
+        ctx.nodes, ctx.grid = (node_y, node_x), grid
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, p = ctx.saved_tensors
+        node_y, node_x = ctx.nodes
+        grid = ctx.grid
+        B, C_, H, W = x.shape
+        S, ks = p.shape[0], p.shape[-1] // grid
+        want_img, want_maps = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dy = _abi.f32c(dy, x.device)
+        d_img = torch.empty_like(x) if want_img else None
+        d_maps = torch.empty_like(p) if want_maps else None
+        ws, nbytes = None, 0
+        if want_maps:
+            nbytes = _abi.load_library().aadff_render_psf_map_blend_stack_bwd_workspace(B, C_, S, H, W, grid, ks)
+            ws = _abi.workspace(x, nbytes)
+        with _abi.on_device(x.device):
+            _abi.call("aadff_render_psf_map_blend_stack_bwd", _abi.ptr(x), _abi.ptr(p), _abi.ptr(dy), _abi.ptr(d_img), _abi.ptr(d_maps),
+                      _abi.ptr(ws), C.c_size_t(nbytes), _host_ptr(node_y), _host_ptr(node_x), B, C_, S, H, W, grid, ks,
+                      _abi.stream_ptr(x.device))
+        return d_img, d_maps, None, None, None
+
+
+def render_psf_map_blend_stack(img, psf_maps, grid, nodes="psf_map"):
+    """aadff.blend.render_psf_map_blend_stack with gradients: img [B,C,H,W], psf_maps [S,C,grid*ks,grid*ks] -> [B,C,S,H,W]; d_img is the sum
+    over the slices, d_maps the sum over the batch.  Under torch.no_grad(), or when neither input requires grad, this IS the forward-only
+    function.  Double backward raises."""
+    from . import blend
+    if not _wants_grad(img, psf_maps):
+        return blend.render_psf_map_blend_stack(img, psf_maps, grid, nodes)
+    assert len(img.shape) == 4, "Input image should be [B, C, H, W]"
+    S, Cpsf, Hpsf, Wpsf = psf_maps.shape
+    assert Hpsf % grid == 0 and Wpsf % grid == 0, "PSF map size should be divisible by grid"
+    ks = int(Hpsf / grid)
+    assert ks % 2 == 1, "PSF kernel size should be odd"
+    B, C_, H, W = img.shape
+    assert C_ == Cpsf, "PSF map should have the same channel as image"
+    node_y, node_x = blend._nodes(nodes, H, W, grid)
+    if img.numel() == 0 or S == 0:
+        return _empty(img, psf_maps, (B, C_, S, H, W))
+    dev = _dev(img)
+    return _BlendStack.apply(_abi.f32c(img, dev), _abi.f32c(psf_maps, dev), node_y, node_x, int(grid)).to(img.device)
+
+
+def render_psf_map_blend(img, psf_map, grid, nodes="psf_map"):
+    """aadff.blend.render_psf_map_blend with gradients: img [B,C,H,W], psf_map [C,grid*ks,grid*ks] -> [B,C,H,W]."""
+    assert len(psf_map.shape) == 3, "PSF map should be [C, grid*ks, grid*ks]"
+    return render_psf_map_blend_stack(img, psf_map[None], grid, nodes)[:, :, 0]
 
 
 # ---------------------------------------------------------------- PSF-network renderers (deeplens/psfnet.py:393-450)

@@ -8,38 +8,14 @@
 // renders one tile of one cell has wave-uniform taps (scalar operands), exactly as a patch tile of conv_psf_map_kernel has; each lane
 // keeps four accumulators per output, one per corner PSF, and blends them at the end with its own fx, fy.  Plain fp32 FMA chains, no
 // atomics, every output written once: bit-reproducible.
-#include <cmath>
-#include <cstdlib>
-#include "common.h"
+#include "blend_axis.h"
 
 namespace aadff {
 
-// One axis of the cell decomposition, by value in the kernel arguments (scalar loads), as PatchBounds is.
-//   cell c (0 <= c < ncell, ncell = max(g - 1, 1)) covers the pixels b[c] <= p < b[c + 1] and blends nodes c and min(c + 1, g - 1);
-//   its tiles are ts[c] <= t < ts[c + 1] of the axis' tile enumeration: an empty cell has no tile, so nothing is launched for it.
-struct BlendAxis {
-    int b[AADFF_MAX_GRID];
-    int ts[AADFF_MAX_GRID];
-    float node[AADFF_MAX_GRID];
-};
-struct BlendCells { BlendAxis y, x; };
-
-constexpr int BT = 32;                        // output tile: BT x BT pixels of one cell
+// from blend_axis.h: BlendAxis, BlendCells, BT, cell_of_tile, blend_frac, fill_axis, check_nodes
 constexpr int BCX = 4, BRR = 4, BQN = BT / BCX;   // lane = (k = lane / 8, q = lane % 8): columns 4q .. 4q+3, rows 4k .. 4k+3
 constexpr int BNW = 4;                        // waves per workgroup: wave w renders slices w, w + 4, ... from the one staged tile
 
-// the cell of tile t: at most 62 scalar steps in front of ks^2 * 64 FMAs per lane
-__device__ __forceinline__ int cell_of_tile(const BlendAxis& a, int ncell, int t) {
-    int c = 0;
-    while (c + 1 < ncell && t >= a.ts[c + 1]) ++c;
-    return c;
-}
-
-// fx of pixel p in the cell between nodes n0 and n1: three roundings (difference, difference, quotient), then the clamp
-__device__ __forceinline__ float blend_frac(int p, float n0, float n1, bool single) {
-    const float f = __fdiv_rn(__fsub_rn((float)p, n0), __fsub_rn(n1, n0));
-    return single ? 0.f : fminf(fmaxf(f, 0.f), 1.f);
-}
 // (1-fy) [(1-fx) a00 + fx a01] + fy [(1-fx) a10 + fx a11] in a fixed order of four roundings per row pair
 __device__ __forceinline__ float blend4(float a00, float a01, float a10, float a11, float fx, float gx, float fy, float gy) {
     const float t0 = __fmaf_rn(fx, a01, __fmul_rn(gx, a00));
@@ -241,29 +217,6 @@ __global__ __launch_bounds__(256) void conv_blend_generic_kernel(
     }
 }
 
-// cells of one axis: b[c] = the first pixel at or right of node c (c = 1 .. g-2; integers p with node[c] <= p), 0 and n at the ends
-static int fill_axis(BlendAxis& a, const float* node, int g, int n) {
-    const int ncell = g > 1 ? g - 1 : 1;
-    for (int i = 0; i < g; ++i) a.node[i] = node[i];
-    a.b[0] = 0;
-    for (int c = 1; c < ncell; ++c) {
-        const double e = std::ceil((double)node[c]);
-        a.b[c] = e <= 0.0 ? 0 : (e >= (double)n ? n : (int)e);
-    }
-    a.b[ncell] = n;
-    a.ts[0] = 0;
-    for (int c = 0; c < ncell; ++c) a.ts[c + 1] = a.ts[c] + (a.b[c + 1] - a.b[c] + BT - 1) / BT;
-    return a.ts[ncell];
-}
-
-static int check_nodes(const float* node, int g, const char* axis) {
-    for (int i = 0; i < g; ++i) AADFF_CHECK_ARG(std::isfinite(node[i]), "render_psf_map_blend: %s[%d] is not finite", axis, i);
-    for (int i = 1; i < g; ++i)
-        AADFF_CHECK_ARG(node[i] > node[i - 1], "render_psf_map_blend: %s is not strictly increasing at index %d (%g after %g)", axis, i,
-                        (double)node[i], (double)node[i - 1]);
-    return 0;
-}
-
 }  // namespace aadff
 
 using namespace aadff;
@@ -271,14 +224,7 @@ using namespace aadff;
 extern "C" int aadff_render_psf_map_blend_stack(const float* img, const float* psf_maps, float* out, const float* node_y, const float* node_x,
                                                 int B, int C, int S, int H, int W, int grid, int ks, aadff_stream_t stream) {
     AADFF_CHECK_ARG(img && psf_maps && out && node_y && node_x, "render_psf_map_blend: NULL pointer");
-    AADFF_CHECK_ARG(B > 0 && C > 0 && S > 0 && H > 0 && W > 0, "render_psf_map_blend: empty tensor (B=%d C=%d S=%d H=%d W=%d)", B, C, S, H, W);
-    AADFF_CHECK_ARG(grid >= 1 && grid <= AADFF_MAX_GRID, "render_psf_map_blend: grid %d outside [1,%d]", grid, AADFF_MAX_GRID);
-    AADFF_CHECK_ARG(ks % 2 == 1, "PSF kernel size should be odd");
-    AADFF_CHECK_ARG(ks >= 1 && ks <= AADFF_MAX_KS, "render_psf_map_blend: ks %d outside [1,%d]", ks, AADFF_MAX_KS);
-    AADFF_CHECK_ARG(ks / 2 < H && ks / 2 < W, "render_psf_map_blend: reflect padding %d needs H,W > pad", ks / 2);
-    AADFF_CHECK_ARG((size_t)B * C <= 65535, "render_psf_map_blend: B*C too large");
-    AADFF_CHECK_ARG((size_t)H + (size_t)BT * grid <= (size_t)65535 * BT && (size_t)W + (size_t)BT * grid <= ((size_t)1 << 30),
-                    "render_psf_map_blend: H=%d W=%d too large for the launch grid", H, W);
+    if (int rc = blend_check_shape(B, C, S, H, W, grid, ks)) return rc;
     if (int rc = check_nodes(node_y, grid, "node_y")) return rc;
     if (int rc = check_nodes(node_x, grid, "node_x")) return rc;
 

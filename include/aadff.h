@@ -195,6 +195,28 @@ int aadff_render_psf_map_stack_bwd(const float* img, const float* psf_maps, cons
 /* Workspace bytes of the call above for the same shape (host arithmetic only, no device needed; monotone in B and S). */
 int aadff_render_psf_map_stack_bwd_workspace(int B, int C, int S, int H, int W, int grid, int ks, size_t* bytes);
 
+/* Gradients of aadff_render_psf_map_blend_stack (csrc/conv_blend_bwd.hip).  With the HAT of node i on row y,
+ *   Hy_i(y) = [k(y) == i] (1 - fy(y)) + [min(k(y) + 1, g - 1) == i] fy(y)      (k, fy of the forward; g == 1: 1 everywhere)
+ * and Hx_j(x) alike, the forward is out[b,c,s,y,x] = sum_{nodes (i,j)} Hy_i(y) Hx_j(x) sum_{u,v} xpad[b,c,y+u,x+v] w_ij[ks-1-u][ks-1-v]
+ * (xpad the reflect-padded image, w_ij tile (i,j) of map s), and
+ *   d_img[b,c,y',x']         = sum_s sum_{(i,j)} sum over the source pixels (y,x) and taps (u,v) whose reflected position is (y',x') of
+ *                              dy[b,c,s,y,x] Hy_i(y) Hx_j(x) w_ij[ks-1-u][ks-1-v]          (the direct term plus the mirror folds)
+ *   d_maps[s,c,i ks+a,j ks+e] = sum_b sum_{(y,x)} dy[b,c,s,y,x] Hy_i(y) Hx_j(x) xpad[b,c,y+ks-1-a,x+ks-1-e]
+ * img [B,C,H,W], psf_maps [S,C,g*ks,g*ks], dy [B,C,S,H,W] contiguous, d_img [B,C,H,W] (sum over the slices), d_maps [S,C,g*ks,g*ks]
+ * (sum over the batch; the tile of a node whose hat holds no pixel is exact zeros).  node_y, node_x: HOST pointers as in the forward;
+ * they get no gradient.  Plain fp32 fmaf sums in a fixed order, the same fx, fy arithmetic as the forward, no float atomics, every
+ * output element written exactly once: bit-reproducible.  A gradient whose pointer is NULL is not computed; both NULL is an error.
+ * d_maps needs `workspace`: device memory of at least aadff_render_psf_map_blend_stack_bwd_workspace bytes (partial sums per 32 x 32
+ * tile of a cell, added in a fixed order by a second kernel); it may be NULL / 0 when d_maps is NULL.  The argument domain and the
+ * messages are the forward's (plus S*C <= 65535); everything is validated before any HIP call. */
+int aadff_render_psf_map_blend_stack_bwd(const float* img, const float* psf_maps, const float* dy,
+                                         float* d_img_or_null, float* d_maps_or_null, void* workspace, size_t workspace_bytes,
+                                         const float* node_y, const float* node_x,
+                                         int B, int C, int S, int H, int W, int grid, int ks, aadff_stream_t stream);
+/* Workspace bytes of the call above: a bound that holds for any nodes (host arithmetic only; monotone in B and S); 0 for a shape the
+ * call rejects (aadff_last_error says why). */
+size_t aadff_render_psf_map_blend_stack_bwd_workspace(int B, int C, int S, int H, int W, int grid, int ks);
+
 /* Gradients of aadff_local_psf_render, i.e. the autograd of deeplens/render_psf.py:76-107 (replicate pad :93, unfold :99,
  * product with the per-pixel kernels and sum :100-104, fold :105).  dy [B,C,H,W], d_img [B,C,H,W] (taps that clamp onto
  * a border pixel all land on it), d_psf [B,H,W,ks,ks] (sum over the channels). */
