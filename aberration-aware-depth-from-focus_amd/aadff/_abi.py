@@ -142,6 +142,10 @@ PROTOTYPES = {
     "aadff_psf_points_staged_fit": [_P, _I, _I, _I, _P, _P, LensConst, _P, _P, _I, _L, _L, _P, _I, _L, _L, _I, _I, _I, _P, _P, _P,
                                     C.POINTER(Stage), _P, _P, _P],
     "aadff_chief_fit_tables": [_P, _P, _P],
+    "aadff_chief_fit_prologue": [_P, _I, _L, _L, _P, _I, _I, _I, _L, _L, LensConst, C.POINTER(Stage), _P, _P, _P],
+    "aadff_psf_points_fit_pts": [_P, _I, _I, _I, _P, _P, LensConst, _P, _P, _I, _L, _L, _P, _I, _L, _L, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "aadff_psf_points_staged_fit_pts": [_P, _I, _I, _I, _P, _P, LensConst, _P, _P, _I, _L, _L, _P, _I, _L, _L, _I, _I, _I, _P, _P, _P,
+                                        C.POINTER(Stage), _P, _P, _P, _P],
     "aadff_psf_points_edge": [_P, _I, _I, _I, _P, _P, LensConst, _P, _P, _I, _L, _L, _P, _I, _L, _L, _I, _F, _P, _P, _P, _P, _P, _I, _P, _P],
     "aadff_strict_edge_retrace": [_P, _I, _I, _P, _P, _I, _I, _P, _P, _P, _I, _P, _F, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],
     "aadff_psf_normalise": [_P, _I, _I, _I, _F, _I, _I, _P, _P],

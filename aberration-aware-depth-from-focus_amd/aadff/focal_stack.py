@@ -58,6 +58,14 @@ def stack_uniform_layout(spp, L=3, spp_chief=GEO_SPP, spp_focus=GEO_SPP):
     return 2 * spp_focus + L * per_l, 2 * spp_focus, 2 * spp_focus + 2 * spp, per_l
 
 
+def pupil_xy_layout(spp, L=3, spp_chief=GEO_SPP):
+    """Layout of the pupil points of a stack (aadff_chief_fit_prologue): per (state, wavelength) one block [main x, main y, chief x,
+    chief y] of spp, spp, spp_chief, spp_chief floats - the (main theta, main r, chief theta, chief r) block of `stack_uniform_layout`
+    with x for theta and y for r.  Returns (floats per state, offset of the chief x row in a block, floats per block)."""
+    per_l = 2 * spp + 2 * spp_chief
+    return L * per_l, 2 * spp, per_l
+
+
 def draw_stack_uniforms(sampler, S, spp, L=3, spp_chief=GEO_SPP, spp_focus=GEO_SPP):
     """Views (u_focus [S,2,spp_focus], u_main [S,L,2,spp], u_chief [S,L,2,spp_chief]) of ONE
     flat draw of S slices (used by tests; the renderer consumes the flat block through strides)."""
@@ -123,7 +131,8 @@ class StackPlan:
         self.guards = {}
         self.turn = 0
         # staged upload (aadff_refocus_staged + aadff_psf_points_staged): the first STAGE_FIRST states' draws are
-        # copied behind the focus traces, the rest by leading workgroups of the PSF launch
+        # copied behind the focus traces, the rest by leading workgroups of the PSF launch - or, with the chief fit's pupil points, by
+        # nobody: the prologue reads them where they are and the PSF launch reads points
         self.stage_counters = torch.zeros(S, dtype=torch.int32, device=dev)
         self.refocus_scratch = torch.zeros(S * 16, dtype=torch.int32, device=dev)     # 64 B per focus state
         self.stage_generation = 0
@@ -131,6 +140,8 @@ class StackPlan:
         self.chief_fit = CHIEF_FIT if chief_fit is None else bool(chief_fit)
         self.fit_weights = torch.empty(S * 3 * 2 * _abi.CHIEF_NODES, dtype=torch.float32, device=dev) if self.chief_fit else None
         self.fit_centres = torch.empty(S * 3 * grid * grid * 4, dtype=torch.float32, device=dev) if self.chief_fit else None
+        # and the pupil points of its draws, mapped once by the weights launch for all the field points (aadff_chief_fit_prologue)
+        self.pupil_xy = torch.empty(S * pupil_xy_layout(spp)[0], dtype=torch.float32, device=dev) if self.chief_fit else None
         self._geo = {}
 
     def uniforms(self, sampler):
@@ -319,19 +330,24 @@ def render_focal_stack_m1(lens, img, depth_plane_mm, focus_mm, grid=11, ks=11, s
         # plan.chief_fit: chief centres from the node rays where no chief ray is vignetted, the weights of this stack's
         # draws first; without it the fit entries get no buffers and are aadff_psf_points / _staged.  (The kernel events attached above
         # go to the PSF-grid kernel alone: the weights and node-ray launches, 40 us, lie in front of them; plan.psf_events has all three.)
+        # The same launch maps the stack's draws to pupil points, which the PSF workgroups then load (no sqrt, sin, cos per ray and
+        # point; the staged entry copies no draws).  AADFF_PSF_LAUNCHES=parent (read by the library per launch): the launches of before.
         if plan.chief_fit:
-            _abi.call("aadff_chief_fit_weights", C.c_void_p(ub + 4 * plan.o_chief), S, 3, GEO_SPP, plan.per, plan.per_l,
-                      None if stage is None else C.byref(stage), _abi.ptr(plan.fit_weights), st)
+            _abi.call("aadff_chief_fit_prologue", C.c_void_p(ub + 4 * plan.o_main), spp, plan.per, plan.per_l,
+                      C.c_void_p(ub + 4 * plan.o_chief), S, 3, GEO_SPP, plan.per, plan.per_l, plan.lc,
+                      None if stage is None else C.byref(stage), _abi.ptr(plan.fit_weights), _abi.ptr(plan.pupil_xy), st)
         if stage is None:
-            _abi.call("aadff_psf_points_fit", _abi.ptr(pts), S, N, 3, _abi.ptr(plan.tab_rgb), _abi.ptr(plan.tab_green),
+            _abi.call("aadff_psf_points_fit_pts", _abi.ptr(pts), S, N, 3, _abi.ptr(plan.tab_rgb), _abi.ptr(plan.tab_green),
                       plan.lc, _abi.ptr(plan.states), C.c_void_p(ub + 4 * plan.o_main), spp, plan.per, plan.per_l,
                       C.c_void_p(ub + 4 * plan.o_chief), GEO_SPP, plan.per, plan.per_l, ks, 1, 1,
-                      _abi.ptr(plan.psf_maps), None, _abi.ptr(plan.flags), _abi.ptr(plan.fit_weights), _abi.ptr(plan.fit_centres), st)
+                      _abi.ptr(plan.psf_maps), None, _abi.ptr(plan.flags), _abi.ptr(plan.fit_weights), _abi.ptr(plan.fit_centres),
+                      _abi.ptr(plan.pupil_xy), st)
         else:
-            _abi.call("aadff_psf_points_staged_fit", _abi.ptr(pts), S, N, 3, _abi.ptr(plan.tab_rgb), _abi.ptr(plan.tab_green),
+            _abi.call("aadff_psf_points_staged_fit_pts", _abi.ptr(pts), S, N, 3, _abi.ptr(plan.tab_rgb), _abi.ptr(plan.tab_green),
                       plan.lc, _abi.ptr(plan.states), C.c_void_p(ub + 4 * plan.o_main), spp, plan.per, plan.per_l,
                       C.c_void_p(ub + 4 * plan.o_chief), GEO_SPP, plan.per, plan.per_l, ks, 1, 1,
-                      _abi.ptr(plan.psf_maps), None, _abi.ptr(plan.flags), C.byref(stage), _abi.ptr(plan.fit_weights), _abi.ptr(plan.fit_centres), st)
+                      _abi.ptr(plan.psf_maps), None, _abi.ptr(plan.flags), C.byref(stage), _abi.ptr(plan.fit_weights), _abi.ptr(plan.fit_centres),
+                      _abi.ptr(plan.pupil_xy), st)
         if plan.psf_events is not None:
             plan.psf_events[1].record()
         if plan.conv_events is not None:
@@ -467,14 +483,17 @@ def render_focal_stack_m1_layered(lens, img, depth_mm, focus_mm, layers=4, grid=
         st_rep = states.view(S, nb).repeat_interleave(L, 0).contiguous()
         u_pairs = u.view(S, slice_stride)[:, o_main:].contiguous()
         base = u_pairs.data_ptr()
-        fit_w = fit_c = None
-        if CHIEF_FIT:       # chief centres of the unvignetted points from the node rays, as on the plan path
+        fit_w = fit_c = pxy = None
+        if CHIEF_FIT:       # chief centres of the unvignetted points from the node rays, as on the plan path, and the
+            #                 pupil points of every pair's draws from the same launch
             fit_w = torch.empty(S * L * 3 * 2 * _abi.CHIEF_NODES, dtype=torch.float32, device=dev)
             fit_c = torch.empty(S * L * 3 * N * 4, dtype=torch.float32, device=dev)
-            _abi.call("aadff_chief_fit_weights", C.c_void_p(base + 4 * 2 * spp), S * L, 3, GEO_SPP, layer_block, per_l, None, _abi.ptr(fit_w), st)
-        _abi.call("aadff_psf_points_fit", _abi.ptr(pts), S * L, N, 3, _abi.ptr(tab_rgb), _abi.ptr(tab_green), lc, _abi.ptr(st_rep),
+            pxy = torch.empty(S * L * pupil_xy_layout(spp)[0], dtype=torch.float32, device=dev)
+            _abi.call("aadff_chief_fit_prologue", C.c_void_p(base), spp, layer_block, per_l, C.c_void_p(base + 4 * 2 * spp), S * L, 3, GEO_SPP,
+                      layer_block, per_l, lc, None, _abi.ptr(fit_w), _abi.ptr(pxy), st)
+        _abi.call("aadff_psf_points_fit_pts", _abi.ptr(pts), S * L, N, 3, _abi.ptr(tab_rgb), _abi.ptr(tab_green), lc, _abi.ptr(st_rep),
                   C.c_void_p(base), spp, layer_block, per_l, C.c_void_p(base + 4 * 2 * spp), GEO_SPP, layer_block, per_l, ks, 1, 1,
-                  _abi.ptr(maps), None, _abi.ptr(flags), _abi.ptr(fit_w), _abi.ptr(fit_c), st)
+                  _abi.ptr(maps), None, _abi.ptr(flags), _abi.ptr(fit_w), _abi.ptr(fit_c), _abi.ptr(pxy), st)
         if ks == 11 and fused:
             # the L candidates of a pixel are computed from one staged band and only the pixel's own layer is written: 1 x the output
             lidx = idx.reshape(B, H, W).to(torch.uint8).contiguous()

@@ -27,6 +27,7 @@ constexpr int kFitChunk = kFitThreads / 64;
 static_assert(kChiefRays == 128 && kChiefNodes <= kChiefRays && kChiefNodes >= 64, "one wave of 64 lanes x 2 rays; every lane's first ray is a node");
 static_assert(kFitMono == (kFitDegree + 1) * (kFitDegree + 2) / 2 && kFitMonoLow == (kFitDegree - 1) * kFitDegree / 2, "monomials by total degree");
 static_assert(kFitMono <= kFitThreads && 2 * kChiefNodes <= kFitThreads, "chief_fit_weights_kernel: one thread per moment / per weight");
+static_assert(kFitBatch % 2 == 0, "chief_fit_weights_kernel<true>: the draws of a batch go through disc_sample2 in pairs");
 static const double h_chief_node_xy[kChiefRays * 2] = AADFF_CHIEF_NODE_XY_INIT;
 static const double h_chief_fit[kFitMono * kChiefNodes] = AADFF_CHIEF_FIT_INIT;
 static const double h_chief_fit_low[kFitMonoLow * kChiefNodes] = AADFF_CHIEF_FIT_LOW_INIT;
@@ -38,15 +39,55 @@ __device__ const double d_chief_fit_low[kFitMonoLow * kChiefNodes] = AADFF_CHIEF
 // median and 2.1e-6 mm at most; 1.3 % of them exceed the tolerance and trace every draw
 constexpr float kChiefFitTol = AADFF_CHIEF_FIT_TOL;
 
-// grid (L, S); u_late: the address u_chief has in the mapped pinned block for states >= late_from (staged launches), else unused
+// The pupil points of a launch with points (PTS, aadff_chief_fit_prologue): the draws of a (state, wavelength) are mapped to the pupil
+// here, once, by disc_sample2 itself, and not again by each of the N point workgroups of the PSF launch.  pupil_xy
+// [S][L] blocks of {main x [spp], main y [spp], chief x [spp_chief], chief y [spp_chief]}: the block of raw draws with every theta
+// row replaced by x and every r row by y, so the PSF kernel reads it through the pointers and strides it reads draws through.
+struct PupilArgs {
+    const float* u_main;      // raw main draws, as the PSF launch gets them; u_main_late: their address in the mapped pinned block
+    const float* u_main_late;
+    long main_ss, main_sl;
+    int spp;
+    float enp_r2, enp_r2_shrunk;
+    float* xy;
+};
+// grid (L, S), with PTS (L, S, 2): z = 0 the chief draws, their points and the weights, z = 1 the points of the main draws; u_late:
+// the address u_chief has in the mapped pinned block for states >= late_from (staged launches), else unused
+template <bool PTS>
 __global__ __launch_bounds__(kFitThreads) void chief_fit_weights_kernel(const float* __restrict__ u_chief, const float* __restrict__ u_late, int late_from,
-                                                                         int L, int spp_chief, long chief_ss, long chief_sl, float* __restrict__ weights) {
+                                                                         int L, int spp_chief, long chief_ss, long chief_sl, float* __restrict__ weights,
+                                                                         PupilArgs pa) {
     __shared__ double buf[kFitChunk][kFitThreads];
     __shared__ double mom[kFitMono];
     __shared__ double wsum[kFitSplit][2][kChiefNodes];
     const int l = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
     const float* ut = (s >= late_from ? u_late : u_chief) + (size_t)s * chief_ss + (size_t)l * chief_sl;
     const float* ur = ut + spp_chief;
+    [[maybe_unused]] float* const pxy = PTS ? pa.xy + (size_t)(s * L + l) * (2 * (size_t)pa.spp + 2 * (size_t)spp_chief) : nullptr;
+    if constexpr (PTS) if (blockIdx.z == 1) {
+        // a workgroup of its own for the main draws, beside the one with the chief draws: the late states' draws come over PCIe, and one
+        // workgroup that waits for both, one after the other, took 28 us where the weights alone take 19.
+        // Two draws at a time through disc_sample2, as the PSF kernel took them; the same batches of loads as below
+        const float* mt = (s >= late_from ? pa.u_main_late : pa.u_main) + (size_t)s * pa.main_ss + (size_t)l * pa.main_sl;
+        const float* mr = mt + pa.spp;
+        for (int i0 = tid; i0 < pa.spp; i0 += kFitBatch * kFitThreads) {
+            float ua[kFitBatch], ub[kFitBatch];
+#pragma unroll
+            for (int q = 0; q < kFitBatch; ++q) {
+                const int i = min(i0 + q * kFitThreads, pa.spp - 1);
+                ua[q] = mt[i]; ub[q] = mr[i];
+            }
+#pragma unroll
+            for (int q = 0; q < kFitBatch; q += 2) {
+                const int ia = i0 + q * kFitThreads, ib = ia + kFitThreads;
+                f2 x2, y2;
+                disc_sample2((f2){ua[q], ua[q + 1]}, (f2){ub[q], ub[q + 1]}, pa.enp_r2, x2, y2);
+                if (ia < pa.spp) { pxy[ia] = x2.x; pxy[pa.spp + ia] = y2.x; }
+                if (ib < pa.spp) { pxy[ib] = x2.y; pxy[pa.spp + ib] = y2.y; }
+            }
+        }
+        return;                                          // whole workgroups
+    }
     double acc[kFitMono];
 #pragma unroll
     for (int j = 0; j < kFitMono; ++j) acc[j] = 0.0;
@@ -56,6 +97,17 @@ __global__ __launch_bounds__(kFitThreads) void chief_fit_weights_kernel(const fl
         for (int q = 0; q < kFitBatch; ++q) {
             const int i = min(i0 + q * kFitThreads, spp_chief - 1);
             ua[q] = ut[i]; ub[q] = ur[i];
+        }
+        if constexpr (PTS) {
+            float* const cxy = pxy + 2 * (size_t)pa.spp;
+#pragma unroll
+            for (int q = 0; q < kFitBatch; q += 2) {
+                const int ia = i0 + q * kFitThreads, ib = ia + kFitThreads;
+                f2 x2, y2;
+                disc_sample2((f2){ua[q], ua[q + 1]}, (f2){ub[q], ub[q + 1]}, pa.enp_r2_shrunk, x2, y2);
+                if (ia < spp_chief) { cxy[ia] = x2.x; cxy[spp_chief + ia] = y2.x; }
+                if (ib < spp_chief) { cxy[ib] = x2.y; cxy[spp_chief + ib] = y2.y; }
+            }
         }
 #pragma unroll
         for (int q = 0; q < kFitBatch; ++q) {
@@ -332,7 +384,9 @@ __device__ __forceinline__ PsfLds psf_lds() {
 }
 
 // FIT: the launch carries fitted chief centres (fit_c); without it the body is the code of a launch that never had any
-template <bool EDGE, class SEQ, bool FIT = false>
+// PTS (fit launches): u_main / u_chief are blocks of pupil points (chief_fit_weights_kernel<true>), an x row where a block of draws has
+// its theta row and a y row for its r row: read, not mapped.  Such a launch stages nothing: its points are in device memory
+template <bool EDGE, class SEQ, bool FIT = false, bool PTS = false>
 __device__ __forceinline__ void psf_points_body(const PsfLds& lds, const float* __restrict__ points, int N, int L,
                                                           const aadff_surface_t* __restrict__ surf_main,
                                                           const aadff_surface_t* __restrict__ surf_chief,
@@ -354,7 +408,13 @@ __device__ __forceinline__ void psf_points_body(const PsfLds& lds, const float* 
     const int n = blockIdx.x, l = blockIdx.y;
     int s = blockIdx.z;
     const int tid = threadIdx.x, kk = g.ks * g.ks;
-    if (stage.src) {
+    static_assert(!PTS || (FIT && !EDGE), "pupil points: launches with fitted centres only");
+    if constexpr (PTS) {
+        // a launch with points that replaces a staged one keeps the counters of the states it would have staged in step with the
+        // caller's generation count: the next launch on them may stage again
+        if (stage.counters && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0 && s >= stage.first_slice)
+            __hip_atomic_fetch_add(stage.counters + s, (unsigned)stage.copy_wgs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else if (stage.src) {
         // Staged launch (aadff_psf_points_staged): the z = 0 plane of the grid is dispatched first; its first
         // stage.copy_wgs workgroups stream the uniform blocks of focus states >= first_slice from pinned host
         // memory into HBM and publish a per-state counter; PSF workgroups of those states wait on it.
@@ -428,6 +488,8 @@ __device__ __forceinline__ void psf_points_body(const PsfLds& lds, const float* 
             const int j1 = act.y ? i1 : i;
             f2 x2, y2;
             // (EDGE: the stack's uniforms are a block the host re-uploads to one address: coherent loads, common.h: fresh)
+            if constexpr (PTS) { x2 = (f2){ut[i], ut[j1]}; y2 = (f2){ur[i], ur[j1]}; }
+            else
             disc_sample2(EDGE ? (f2){fresh(ut + i), fresh(ut + j1)} : (f2){ut[i], ut[j1]}, EDGE ? (f2){fresh(ur + i), fresh(ur + j1)} : (f2){ur[i], ur[j1]},
                          lc.enp_r2_shrunk, x2, y2);
             const Ray2 r = trace_pair_to_sensor<SEQ>(px, py, depth, x2, y2, lc.enp_z, act, surf_chief, lc.n_surf, st.d_sensor, nan_flag);
@@ -442,7 +504,8 @@ __device__ __forceinline__ void psf_points_body(const PsfLds& lds, const float* 
 #else
         for (int i = tid; i < n_chief; i += kPsfThreads) {
             float x2, y2;
-            disc_sample(ut[i], ur[i], lc.enp_r2_shrunk, x2, y2);
+            if constexpr (PTS) { x2 = ut[i]; y2 = ur[i]; }
+            else disc_sample(ut[i], ur[i], lc.enp_r2_shrunk, x2, y2);
             Ray r = ray_to(px, py, depth, x2, y2, lc.enp_z);
             trace_range<false>(surf_chief, 0, lc.n_surf, true, r, nan_flag);
             propagate_to(r, st.d_sensor);
@@ -506,6 +569,8 @@ __device__ __forceinline__ void psf_points_body(const PsfLds& lds, const float* 
             const i2 act = {-1, i1 < cn ? -1 : 0};
             const int j1 = act.y ? i1 : i;
             f2 x2, y2;
+            if constexpr (PTS) { x2 = (f2){ut[c0 + i], ut[c0 + j1]}; y2 = (f2){ur[c0 + i], ur[c0 + j1]}; }
+            else
             disc_sample2(EDGE ? (f2){fresh(ut + c0 + i), fresh(ut + c0 + j1)} : (f2){ut[c0 + i], ut[c0 + j1]},
                          EDGE ? (f2){fresh(ur + c0 + i), fresh(ur + c0 + j1)} : (f2){ur[c0 + i], ur[c0 + j1]}, lc.enp_r2, x2, y2);
             Ray2 r;
@@ -560,7 +625,8 @@ __device__ __forceinline__ void psf_points_body(const PsfLds& lds, const float* 
         const i2 act = {-1, i1 < spp ? -1 : 0};
         const int j1 = act.y ? i1 : i;
         f2 x2, y2;
-        disc_sample2((f2){ut[i], ut[j1]}, (f2){ur[i], ur[j1]}, lc.enp_r2, x2, y2);
+        if constexpr (PTS) { x2 = (f2){ut[i], ut[j1]}; y2 = (f2){ur[i], ur[j1]}; }
+        else disc_sample2((f2){ut[i], ut[j1]}, (f2){ur[i], ur[j1]}, lc.enp_r2, x2, y2);
         const Ray2 r = trace_pair_to_sensor<SEQ>(px, py, depth, x2, y2, lc.enp_z, act, tab, lc.n_surf, st.d_sensor, nan_flag);
         if (!(EDGE && edge_defer(g, edge, r.ox.x, r.oy.x, r.ra.x > 0.f, cx, cy, s * L + l, n, i))) splat_hit(hist, g, r.ox.x, r.oy.x, r.ra.x, cx, cy);
         if (!(EDGE && edge_defer(g, edge, r.ox.y, r.oy.y, r.ra.y > 0.f, cx, cy, s * L + l, n, j1))) splat_hit(hist, g, r.ox.y, r.oy.y, r.ra.y, cx, cy);
@@ -569,7 +635,8 @@ __device__ __forceinline__ void psf_points_body(const PsfLds& lds, const float* 
 #else
     for (int i = tid; i < spp; i += kPsfThreads) {
         float x2, y2;
-        disc_sample(ut[i], ur[i], lc.enp_r2, x2, y2);
+        if constexpr (PTS) { x2 = ut[i]; y2 = ur[i]; }
+        else disc_sample(ut[i], ur[i], lc.enp_r2, x2, y2);
         Ray r = ray_to(px, py, depth, x2, y2, lc.enp_z);
         trace_range<false>(tab, 0, lc.n_surf, true, r, nan_flag);
         propagate_to(r, st.d_sensor);
@@ -586,9 +653,11 @@ __device__ __forceinline__ void psf_points_body(const PsfLds& lds, const float* 
     if (nan_flag && flags) atomicOr(flags, 1);
 }
 
-// Chief-centre fit, the node rays: one wave per (point, wavelength, state) traces the kChiefRays node and guard-ring rays of the shrunk
+// Chief-centre fit, the node rays: one wave per (point, state) traces the kChiefRays node and guard-ring rays of the shrunk
 // pupil, lane i the rays i and i + 64, through the PSF kernel's own trace_pair_to_sensor, and leaves {hit x, hit y, ok, 0} in
-// out [S][L][N][4].  The hit is h_0 + sum_k w_k (h_k - h_0) with h_0 the centre node's (an error in sum w then multiplies a spot size,
+// out [S][L][N][4] for the wavelengths [l0, l1): the chief table, the nodes, the point and the state are the same for every
+// wavelength, so the rays are, and only the weights of (state, wavelength) differ - one trace, l1 - l0 weighted sums in the order a wave
+// per wavelength took them (AADFF_CHIEF_CENTRES=per_wavelength launches this kernel with such waves, l1 = l0 + 1: the same bits).  The hit is h_0 + sum_k w_k (h_k - h_0) with h_0 the centre node's (an error in sum w then multiplies a spot size,
 // not a sensor coordinate); ok unless a node or ring ray died (vignetting reaches into the shrunk pupil: the hit is no polynomial
 // there) or the degree-d and degree-(d - 2) hits disagree.  A kernel of its own, not a first pass of the PSF kernel's workgroups: there
 // one wave traced while seven waited, the workgroup kept its LDS and wave slots meanwhile, and of the 45 % of the instructions saved
@@ -597,7 +666,7 @@ constexpr int kNodeWaves = 4;
 template <class SEQ>
 __device__ __forceinline__ void chief_fit_centre_body(const float* __restrict__ points, int N, int L, const aadff_surface_t* __restrict__ surf_chief,
                                                       aadff_lens_const_t lc, const aadff_lens_state_t* __restrict__ states,
-                                                      const float* __restrict__ fit_w, float* __restrict__ out, int n, int l, int s) {
+                                                      const float* __restrict__ fit_w, float* __restrict__ out, int n, int l0, int l1, int s) {
     const int i = threadIdx.x & 63, j1 = i + 64;
     const float d_sensor = fresh_uniform(&states[s].d_sensor), tan_hfov = fresh_uniform(&states[s].tan_hfov);
     const float* pt = points + ((size_t)s * N + n) * 3;
@@ -609,30 +678,35 @@ __device__ __forceinline__ void chief_fit_centre_body(const float* __restrict__ 
     const f2 x2 = (f2){d_chief_node_xy[2 * i], d_chief_node_xy[2 * j1]} * rs, y2 = (f2){d_chief_node_xy[2 * i + 1], d_chief_node_xy[2 * j1 + 1]} * rs;
     int nan_flag = 0;                                               // a NaN in a ray that is not one of the reference's is no error of the reference's
     const Ray2 r = trace_pair_to_sensor<SEQ>(px, py, depth, x2, y2, lc.enp_z, (i2){-1, -1}, surf_chief, lc.n_surf, d_sensor, nan_flag);
-    const float* w = fit_w + (size_t)(s * L + l) * 2 * kChiefNodes;
     const float hx0 = __shfl(r.ox.x, 0, kWave), hy0 = __shfl(r.oy.x, 0, kWave);
     const bool node1 = j1 < kChiefNodes;                            // i < 64 <= kChiefNodes: a lane's first ray always is a node
-    const f2 wd = {w[i], node1 ? w[j1] : 0.f}, wl = {w[kChiefNodes + i], node1 ? w[kChiefNodes + j1] : 0.f};
     const f2 ex = r.ox - hx0, ey = r.oy - hy0;
-    const f2 adx = wd * ex, ady = wd * ey, alx = wl * ex, aly = wl * ey;
-    const float fx = wave_sum(adx.x + adx.y), fy = wave_sum(ady.x + ady.y);
-    const float gx = wave_sum(alx.x + alx.y), gy = wave_sum(aly.x + aly.y);
-    const bool all_alive = __all(r.alive.x != 0 && r.alive.y != 0);
-    if (i == 0) {
-        const bool ok = all_alive && fabsf(fx - gx) <= kChiefFitTol && fabsf(fy - gy) <= kChiefFitTol;
-        *reinterpret_cast<float4*>(out + ((size_t)(s * L + l) * N + n) * 4) = make_float4(hx0 + fx, hy0 + fy, ok ? 1.f : 0.f, 0.f);
+    const bool all_alive = __all(r.alive.x != 0 && r.alive.y != 0);  // guard (a): the rays', shared; guard (b): each wavelength's own
+    for (int l = l0; l < l1; ++l) {
+        const float* w = fit_w + (size_t)(s * L + l) * 2 * kChiefNodes;
+        const f2 wd = {w[i], node1 ? w[j1] : 0.f}, wl = {w[kChiefNodes + i], node1 ? w[kChiefNodes + j1] : 0.f};
+        const f2 adx = wd * ex, ady = wd * ey, alx = wl * ex, aly = wl * ey;
+        const float fx = wave_sum(adx.x + adx.y), fy = wave_sum(ady.x + ady.y);
+        const float gx = wave_sum(alx.x + alx.y), gy = wave_sum(aly.x + aly.y);
+        if (i == 0) {
+            const bool ok = all_alive && fabsf(fx - gx) <= kChiefFitTol && fabsf(fy - gy) <= kChiefFitTol;
+            *reinterpret_cast<float4*>(out + ((size_t)(s * L + l) * N + n) * 4) = make_float4(hx0 + fx, hy0 + fy, ok ? 1.f : 0.f, 0.f);
+        }
     }
 }
-// grid (ceil(N / kNodeWaves), L, S); surf_main: the table whose kinds decide the trace with surf_chief's, as in psf_points_dispatch
+// grid (ceil(N / kNodeWaves), 1, S), or with per_l (ceil(N / kNodeWaves), L, S) and a wave per wavelength; surf_main: the table whose
+// kinds decide the trace with surf_chief's, as in psf_points_dispatch (the kinds are the same in every wavelength's table)
 __global__ __launch_bounds__(kNodeWaves * 64) void chief_fit_centres_kernel(const float* __restrict__ points, int N, int L,
                                                                              const aadff_surface_t* __restrict__ surf_main,
                                                                              const aadff_surface_t* __restrict__ surf_chief, aadff_lens_const_t lc,
                                                                              const aadff_lens_state_t* __restrict__ states,
-                                                                             const float* __restrict__ fit_w, int trace_mode, float* __restrict__ out) {
-    const int n = blockIdx.x * kNodeWaves + (threadIdx.x >> 6), l = blockIdx.y, s = blockIdx.z;
+                                                                             const float* __restrict__ fit_w, int trace_mode, int per_l,
+                                                                             float* __restrict__ out) {
+    const int n = blockIdx.x * kNodeWaves + (threadIdx.x >> 6), s = blockIdx.z;
+    const int l0 = per_l ? (int)blockIdx.y : 0, l1 = per_l ? l0 + 1 : L;
     if (n >= N) return;                                             // whole waves
-    auto body = [&](auto seq) { chief_fit_centre_body<decltype(seq)>(points, N, L, surf_chief, lc, states, fit_w, out, n, l, s); };
-    [[maybe_unused]] const int path = psf_seq_path(surf_main + (size_t)l * lc.n_surf, surf_chief, lc.n_surf, trace_mode == 1);
+    auto body = [&](auto seq) { chief_fit_centre_body<decltype(seq)>(points, N, L, surf_chief, lc, states, fit_w, out, n, l0, l1, s); };
+    [[maybe_unused]] const int path = psf_seq_path(surf_main + (size_t)l0 * lc.n_surf, surf_chief, lc.n_surf, trace_mode == 1);
 #ifndef AADFF_PSF_NO_SEQ
     if (path == 1) body(seq::Rf50mm{});
     else if (path == 2) body(seq::F28{});
@@ -645,7 +719,7 @@ __global__ __launch_bounds__(kNodeWaves * 64) void chief_fit_centres_kernel(cons
 // differ); this workgroup's own is the one checked, and the chief table where the chief pass runs.  trace_mode (AADFF_PSF_TRACE):
 // 1 = the loop for every lens; 2 = as 0, and a workgroup that takes a compiled sequence ORs kPsfSeqFlag << (path - 1) into flags.
 constexpr int kPsfSeqFlag = 256;
-template <bool FIT>
+template <bool FIT, bool PTS>
 __device__ __forceinline__ void psf_points_dispatch(const float* __restrict__ points, int N, int L,
                                                     const aadff_surface_t* __restrict__ surf_main,
                                                     const aadff_surface_t* __restrict__ surf_chief,
@@ -657,7 +731,7 @@ __device__ __forceinline__ void psf_points_dispatch(const float* __restrict__ po
                                                     float* centre_out, int* flags, StageArgs stage, int trace_mode, const float* __restrict__ fit_c) {
     const PsfLds lds = psf_lds<false>();
     auto body = [&](auto seq) {
-        psf_points_body<false, decltype(seq), FIT>(lds, points, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_ss, main_sl, u_chief, spp_chief, chief_ss,
+        psf_points_body<false, decltype(seq), FIT, PTS>(lds, points, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_ss, main_sl, u_chief, spp_chief, chief_ss,
                                               chief_sl, g, centre_mode, map_grid, psf, centre_out, flags, stage, EdgeArgs{}, fit_c);
     };
     [[maybe_unused]] const int path = psf_seq_path(surf_main + (size_t)blockIdx.y * lc.n_surf, centre_mode == 1 ? surf_chief : nullptr, lc.n_surf, trace_mode == 1);
@@ -671,7 +745,7 @@ __device__ __forceinline__ void psf_points_dispatch(const float* __restrict__ po
 }
 
 // TIMED: the same code under a second name for the launches that carry aadff_time_next_launch's events (see conv.hip)
-template <bool TIMED, bool FIT>
+template <bool TIMED, bool FIT, bool PTS = false>
 __global__ __launch_bounds__(kPsfThreads, 6) void psf_points_kernel(const float* __restrict__ points, int N, int L,
                                                           const aadff_surface_t* __restrict__ surf_main,
                                                           const aadff_surface_t* __restrict__ surf_chief,
@@ -681,7 +755,7 @@ __global__ __launch_bounds__(kPsfThreads, 6) void psf_points_kernel(const float*
                                                           long main_sl, const float* __restrict__ u_chief,
                                                           int spp_chief, long chief_ss, long chief_sl, SplatGeom g, int centre_mode, int map_grid, float* psf,
                                                           float* centre_out, int* flags, StageArgs stage, int trace_mode, const float* __restrict__ fit_c) {
-    psf_points_dispatch<FIT>(points, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_ss, main_sl, u_chief, spp_chief, chief_ss, chief_sl, g,
+    psf_points_dispatch<FIT, PTS>(points, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_ss, main_sl, u_chief, spp_chief, chief_ss, chief_sl, g,
                         centre_mode, map_grid, psf, centre_out, flags, stage, trace_mode, fit_c);
 }
 
@@ -960,12 +1034,29 @@ static bool psf_chief_full() {
     return e && strcmp(e, "full") == 0;
 }
 
+// The launches of before, for A/B runs and tests; all read per launch.  AADFF_PSF_POINTS=raw: the entries with pupil points map raw draws
+// in every workgroup again (and stage them), the prologue computes the weights alone.  AADFF_CHIEF_CENTRES=per_wavelength: a node-ray
+// wave per (point, wavelength, state).  AADFF_PSF_LAUNCHES=parent: both.
+static bool psf_launches_parent() {
+    const char* e = getenv("AADFF_PSF_LAUNCHES");
+    return e && strcmp(e, "parent") == 0;
+}
+static bool psf_points_raw() {
+    const char* e = getenv("AADFF_PSF_POINTS");
+    return (e && strcmp(e, "raw") == 0) || psf_launches_parent();
+}
+static bool chief_centres_per_wavelength() {
+    const char* e = getenv("AADFF_CHIEF_CENTRES");
+    return (e && strcmp(e, "per_wavelength") == 0) || psf_launches_parent();
+}
+
+// pupil_xy: NULL, or the points aadff_chief_fit_prologue made of u_main / u_chief (same sizes and strides)
 static int psf_points_launch(const float* points, int S, int N, int L, const aadff_surface_t* surf_main,
                      const aadff_surface_t* surf_chief, aadff_lens_const_t lc, const aadff_lens_state_t* states,
                      const float* u_main, int spp, long main_stride_s, long main_stride_l, const float* u_chief,
                      int spp_chief, long chief_stride_s, long chief_stride_l, int ks, int centre_mode,
                      int map_layout, float* psf, float* centre_out_or_null, int* flags_or_null,
-                     const aadff_stage_t* stage, const float* fit_weights, float* fit_centres, aadff_stream_t stream) {
+                     const aadff_stage_t* stage, const float* fit_weights, float* fit_centres, const float* pupil_xy, aadff_stream_t stream) {
     AADFF_CHECK_ARG(points && surf_main && states && u_main && psf, "psf_points: NULL pointer");
     AADFF_CHECK_ARG(centre_mode == 0 || (surf_chief && u_chief && spp_chief > 0), "psf_points: chief-ray centre needs surf_chief/u_chief");
     AADFF_CHECK_ARG(S > 0 && S <= 65535 && N > 0 && L > 0 && L <= 65535 && spp > 0, "psf_points: bad sizes S=%d N=%d L=%d spp=%d", S, N, L, spp);
@@ -1002,15 +1093,28 @@ static int psf_points_launch(const float* points, int S, int N, int L, const aad
     const float* fit_c = nullptr;
     if (fit_weights && centre_mode == 1 && spp_chief >= 4 * kChiefRays && !psf_chief_full()) {
         AADFF_CHECK_ARG(fit_centres, "psf_points_fit: fit_weights without fit_centres");
-        hipLaunchKernelGGL(chief_fit_centres_kernel, dim3((N + kNodeWaves - 1) / kNodeWaves, L, S), dim3(kNodeWaves * 64), 0, (hipStream_t)stream, points, N, L,
-                           surf_main, surf_chief, lc, states, fit_weights, trace_mode, fit_centres);
+        const int per_l = chief_centres_per_wavelength();
+        hipLaunchKernelGGL(chief_fit_centres_kernel, dim3((N + kNodeWaves - 1) / kNodeWaves, per_l ? L : 1, S), dim3(kNodeWaves * 64), 0, (hipStream_t)stream,
+                           points, N, L, surf_main, surf_chief, lc, states, fit_weights, trace_mode, per_l, fit_centres);
         AADFF_CHECK_LAUNCH();
         fit_c = fit_centres;
     }
+    // points in place of draws: fit launches only (a launch that traces every chief ray is the launch of before, staging included)
+    const bool pts = fit_c && pupil_xy && !psf_points_raw();
+    if (pts) {
+        main_stride_l = chief_stride_l = 2 * (long)spp + 2 * (long)spp_chief;
+        main_stride_s = chief_stride_s = L * main_stride_l;
+        u_main = pupil_xy;
+        u_chief = pupil_xy + 2 * (long)spp;
+        sa.src = nullptr;                                                // no copy plane, no wait: nothing reads the staged draws
+        sa.dst = nullptr;
+    }
     hipEvent_t ev0 = g_time_start, ev1 = g_time_stop;                    // aadff_time_next_launch
     g_time_start = g_time_stop = nullptr;
-    // four instances of one kernel: with or without the events of aadff_time_next_launch, with or without fitted centres
-    const auto kern = fit_c ? (ev0 ? psf_points_kernel<true, true> : psf_points_kernel<false, true>)
+    // six instances of one kernel: with or without the events of aadff_time_next_launch; without fitted centres, with them, and with them
+    // and pupil points
+    const auto kern = pts   ? (ev0 ? psf_points_kernel<true, true, true> : psf_points_kernel<false, true, true>)
+                    : fit_c ? (ev0 ? psf_points_kernel<true, true> : psf_points_kernel<false, true>)
                             : (ev0 ? psf_points_kernel<true, false> : psf_points_kernel<false, false>);
     if (ev0)
         hipExtLaunchKernelGGL(kern, dim3(N, L, sa.src ? S + 1 : S), dim3(kPsfThreads), (size_t)ks * ks * sizeof(float), (hipStream_t)stream,
@@ -1034,7 +1138,7 @@ int aadff_psf_points(const float* points, int S, int N, int L, const aadff_surfa
                      aadff_stream_t stream) {
     return psf_points_launch(points, S, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_stride_s, main_stride_l,
                              u_chief, spp_chief, chief_stride_s, chief_stride_l, ks, centre_mode, map_layout, psf,
-                             centre_out_or_null, flags_or_null, nullptr, nullptr, nullptr, stream);
+                             centre_out_or_null, flags_or_null, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int aadff_psf_points_fit(const float* points, int S, int N, int L, const aadff_surface_t* surf_main,
@@ -1045,7 +1149,7 @@ int aadff_psf_points_fit(const float* points, int S, int N, int L, const aadff_s
                          const float* fit_weights_or_null, float* fit_centres, aadff_stream_t stream) {
     return psf_points_launch(points, S, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_stride_s, main_stride_l,
                              u_chief, spp_chief, chief_stride_s, chief_stride_l, ks, centre_mode, map_layout, psf,
-                             centre_out_or_null, flags_or_null, nullptr, fit_weights_or_null, fit_centres, stream);
+                             centre_out_or_null, flags_or_null, nullptr, fit_weights_or_null, fit_centres, nullptr, stream);
 }
 
 int aadff_psf_points_staged(const float* points, int S, int N, int L, const aadff_surface_t* surf_main,
@@ -1057,7 +1161,7 @@ int aadff_psf_points_staged(const float* points, int S, int N, int L, const aadf
     AADFF_CHECK_ARG(stage, "psf_points_staged: NULL stage");
     return psf_points_launch(points, S, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_stride_s, main_stride_l,
                              u_chief, spp_chief, chief_stride_s, chief_stride_l, ks, centre_mode, map_layout, psf,
-                             centre_out_or_null, flags_or_null, stage, nullptr, nullptr, stream);
+                             centre_out_or_null, flags_or_null, stage, nullptr, nullptr, nullptr, stream);
 }
 
 int aadff_psf_points_staged_fit(const float* points, int S, int N, int L, const aadff_surface_t* surf_main,
@@ -1069,31 +1173,81 @@ int aadff_psf_points_staged_fit(const float* points, int S, int N, int L, const 
     AADFF_CHECK_ARG(stage, "psf_points_staged_fit: NULL stage");
     return psf_points_launch(points, S, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_stride_s, main_stride_l,
                              u_chief, spp_chief, chief_stride_s, chief_stride_l, ks, centre_mode, map_layout, psf,
-                             centre_out_or_null, flags_or_null, stage, fit_weights_or_null, fit_centres, stream);
+                             centre_out_or_null, flags_or_null, stage, fit_weights_or_null, fit_centres, nullptr, stream);
+}
+
+int aadff_psf_points_fit_pts(const float* points, int S, int N, int L, const aadff_surface_t* surf_main,
+                             const aadff_surface_t* surf_chief, aadff_lens_const_t lc, const aadff_lens_state_t* states,
+                             const float* u_main, int spp, long main_stride_s, long main_stride_l, const float* u_chief,
+                             int spp_chief, long chief_stride_s, long chief_stride_l, int ks, int centre_mode,
+                             int map_layout, float* psf, float* centre_out_or_null, int* flags_or_null,
+                             const float* fit_weights_or_null, float* fit_centres, const float* pupil_xy_or_null, aadff_stream_t stream) {
+    return psf_points_launch(points, S, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_stride_s, main_stride_l,
+                             u_chief, spp_chief, chief_stride_s, chief_stride_l, ks, centre_mode, map_layout, psf,
+                             centre_out_or_null, flags_or_null, nullptr, fit_weights_or_null, fit_centres, pupil_xy_or_null, stream);
+}
+
+int aadff_psf_points_staged_fit_pts(const float* points, int S, int N, int L, const aadff_surface_t* surf_main,
+                                    const aadff_surface_t* surf_chief, aadff_lens_const_t lc, const aadff_lens_state_t* states,
+                                    const float* u_main, int spp, long main_stride_s, long main_stride_l, const float* u_chief,
+                                    int spp_chief, long chief_stride_s, long chief_stride_l, int ks, int centre_mode,
+                                    int map_layout, float* psf, float* centre_out_or_null, int* flags_or_null,
+                                    const aadff_stage_t* stage, const float* fit_weights_or_null, float* fit_centres,
+                                    const float* pupil_xy_or_null, aadff_stream_t stream) {
+    AADFF_CHECK_ARG(stage, "psf_points_staged_fit_pts: NULL stage");
+    return psf_points_launch(points, S, N, L, surf_main, surf_chief, lc, states, u_main, spp, main_stride_s, main_stride_l,
+                             u_chief, spp_chief, chief_stride_s, chief_stride_l, ks, centre_mode, map_layout, psf,
+                             centre_out_or_null, flags_or_null, stage, fit_weights_or_null, fit_centres, pupil_xy_or_null, stream);
+}
+
+// the weights of a stack's chief draws and, with pa.xy, the pupil points of its main and chief draws: one launch
+static int chief_fit_prologue_launch(const char* who, const float* u_chief, int S, int L, int spp_chief, long chief_stride_s, long chief_stride_l,
+                                     const aadff_stage_t* stage_or_null, float* weights, PupilArgs pa, aadff_stream_t stream) {
+    AADFF_CHECK_ARG(u_chief && weights, "%s: NULL pointer", who);
+    AADFF_CHECK_ARG(S > 0 && S <= 65535 && L > 0 && L <= 65535 && spp_chief > 0, "%s: bad sizes S=%d L=%d spp_chief=%d", who, S, L, spp_chief);
+    const float* u_late = u_chief;
+    int late_from = S;
+    pa.u_main_late = pa.u_main;
+    if (stage_or_null && stage_or_null->first_slice < S) {
+        // the draws of the states >= first_slice are still on the host when this kernel runs: read them where the late path of the
+        // PSF launch does, at u_chief's (and u_main's) place in the mapped pinned block
+        const aadff_stage_t* stage = stage_or_null;
+        AADFF_CHECK_ARG(stage->src_host && stage->dst_dev && stage->first_slice >= 0 && stage->slice_stride > 0, "%s: bad aadff_stage_t", who);
+        AADFF_CHECK_ARG(u_chief >= stage->dst_dev && u_chief < stage->dst_dev + (long)S * stage->slice_stride,
+                        "%s: u_chief must point into dst_dev[0 .. S*slice_stride)", who);
+        AADFF_CHECK_ARG(!pa.xy || (pa.u_main >= stage->dst_dev && pa.u_main < stage->dst_dev + (long)S * stage->slice_stride),
+                        "%s: u_main must point into dst_dev[0 .. S*slice_stride)", who);
+        void* mapped;
+        if (const int rc = mapped_host_pointer(stage->src_host, "chief_fit_weights: src_host is", &mapped)) return rc;
+        u_late = reinterpret_cast<const float*>(mapped) + (u_chief - stage->dst_dev);
+        if (pa.xy) pa.u_main_late = reinterpret_cast<const float*>(mapped) + (pa.u_main - stage->dst_dev);
+        late_from = stage->first_slice;
+    }
+    if (pa.xy)
+        hipLaunchKernelGGL(chief_fit_weights_kernel<true>, dim3(L, S, 2), dim3(kFitThreads), 0, (hipStream_t)stream, u_chief, u_late, late_from, L, spp_chief,
+                           chief_stride_s, chief_stride_l, weights, pa);
+    else
+        hipLaunchKernelGGL(chief_fit_weights_kernel<false>, dim3(L, S), dim3(kFitThreads), 0, (hipStream_t)stream, u_chief, u_late, late_from, L, spp_chief,
+                           chief_stride_s, chief_stride_l, weights, pa);
+    AADFF_CHECK_LAUNCH();
+    return 0;
 }
 
 int aadff_chief_fit_weights(const float* u_chief, int S, int L, int spp_chief, long chief_stride_s, long chief_stride_l,
                             const aadff_stage_t* stage_or_null, float* weights, aadff_stream_t stream) {
-    AADFF_CHECK_ARG(u_chief && weights, "chief_fit_weights: NULL pointer");
-    AADFF_CHECK_ARG(S > 0 && S <= 65535 && L > 0 && L <= 65535 && spp_chief > 0, "chief_fit_weights: bad sizes S=%d L=%d spp_chief=%d", S, L, spp_chief);
-    const float* u_late = u_chief;
-    int late_from = S;
-    if (stage_or_null && stage_or_null->first_slice < S) {
-        // the draws of the states >= first_slice are still on the host when this kernel runs: read them where the late path of the
-        // PSF launch does, at u_chief's place in the mapped pinned block
-        const aadff_stage_t* stage = stage_or_null;
-        AADFF_CHECK_ARG(stage->src_host && stage->dst_dev && stage->first_slice >= 0 && stage->slice_stride > 0, "chief_fit_weights: bad aadff_stage_t");
-        AADFF_CHECK_ARG(u_chief >= stage->dst_dev && u_chief < stage->dst_dev + (long)S * stage->slice_stride,
-                        "chief_fit_weights: u_chief must point into dst_dev[0 .. S*slice_stride)");
-        void* mapped;
-        if (const int rc = mapped_host_pointer(stage->src_host, "chief_fit_weights: src_host is", &mapped)) return rc;
-        u_late = reinterpret_cast<const float*>(mapped) + (u_chief - stage->dst_dev);
-        late_from = stage->first_slice;
+    return chief_fit_prologue_launch("chief_fit_weights", u_chief, S, L, spp_chief, chief_stride_s, chief_stride_l, stage_or_null, weights, PupilArgs{}, stream);
+}
+
+int aadff_chief_fit_prologue(const float* u_main, int spp, long main_stride_s, long main_stride_l, const float* u_chief, int S, int L, int spp_chief,
+                             long chief_stride_s, long chief_stride_l, aadff_lens_const_t lc, const aadff_stage_t* stage_or_null, float* weights,
+                             float* pupil_xy, aadff_stream_t stream) {
+    AADFF_CHECK_ARG(u_main && pupil_xy && spp > 0, "chief_fit_prologue: NULL pointer or spp=%d", spp);
+    PupilArgs pa{};
+    if (!psf_points_raw()) {                                             // (raw: the PSF launch will not read the points)
+        pa.u_main = u_main; pa.main_ss = main_stride_s; pa.main_sl = main_stride_l; pa.spp = spp;
+        pa.enp_r2 = lc.enp_r2; pa.enp_r2_shrunk = lc.enp_r2_shrunk; pa.xy = pupil_xy;
     }
-    hipLaunchKernelGGL(chief_fit_weights_kernel, dim3(L, S), dim3(kFitThreads), 0, (hipStream_t)stream, u_chief, u_late, late_from, L, spp_chief,
-                       chief_stride_s, chief_stride_l, weights);
-    AADFF_CHECK_LAUNCH();
-    return 0;
+    return chief_fit_prologue_launch("chief_fit_prologue", u_chief, S, L, spp_chief, chief_stride_s, chief_stride_l, stage_or_null, weights, pa, stream);
 }
 
 int aadff_chief_fit_tables(double* node_xy, double* fit, double* fit_low) {

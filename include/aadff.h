@@ -706,7 +706,7 @@ int aadff_psf_points_staged(const float* points, int S, int N, int L,
  *     stream - the draws of states >= first_slice are then read from the pinned host block, where they still are.
  *   aadff_psf_points_fit / aadff_psf_points_staged_fit: aadff_psf_points / _staged with that buffer and fit_centres, scratch of
  *     [S][L][N][4] floats (16-byte aligned).  With centre_mode 1 and spp_chief >= 4 * AADFF_CHIEF_RAYS, a launch of one wave per
- *     (point, wavelength, state) in front of the PSF launch traces the nodes and a guard ring at 1.05 x the shrunk-pupil radius
+ *     (point, state) in front of the PSF launch traces the nodes and a guard ring at 1.05 x the shrunk-pupil radius
  *     (AADFF_CHIEF_RAYS rays in all); the fitted centre stands if every one of those rays is alive and the degree-d and
  *     degree-(d - 2) centres agree; otherwise the PSF workgroup traces every draw, as without weights and with the same bits.
  *     fit_weights_or_null = NULL, or AADFF_PSF_CHIEF=full in the environment (read per launch), is aadff_psf_points / _staged.
@@ -734,6 +734,42 @@ int aadff_psf_points_staged_fit(const float* points, int S, int N, int L,
                      int ks, int centre_mode, int map_layout, float* psf, float* centre_out_or_null,
                      int* flags_or_null, const aadff_stage_t* stage, const float* fit_weights_or_null, float* fit_centres, aadff_stream_t stream);
 int aadff_chief_fit_tables(double* node_xy, double* fit, double* fit_low);
+
+/* Pupil points once per stack.  The pupil point of a draw depends on (state, wavelength, draw) alone, and every one of the N point
+ * workgroups of a (state, wavelength) used to map the same draws again.  A fit launch can read the points instead:
+ *   aadff_chief_fit_prologue: aadff_chief_fit_weights (same weights, to the bit) which also maps the main draws (lc.enp_r2) and the
+ *     chief draws (lc.enp_r2_shrunk) of every (state, wavelength) with the PSF kernel's own mapping and writes them to pupil_xy:
+ *     [S][L] blocks of {main x [spp], main y [spp], chief x [spp_chief], chief y [spp_chief]} floats - the block of draws with x in
+ *     place of theta and y in place of r.  u_main / u_chief and their strides are what the PSF launch gets; with a stage, both must
+ *     point into dst_dev and the draws of states >= first_slice are read from the pinned host block.
+ *   aadff_psf_points_fit_pts / aadff_psf_points_staged_fit_pts: aadff_psf_points_fit / _staged_fit with those points.  Where the launch
+ *     carries fitted centres (see above) its workgroups load points instead of draws; nothing reads the device copy of the draws then,
+ *     so the staged entry copies nothing, waits for nothing and only keeps stage->counters in step with stage->generation (a later
+ *     launch on the same counters may stage again).  A launch without fitted centres (no weights, centre_mode 0, few chief draws,
+ *     AADFF_PSF_CHIEF=full), pupil_xy_or_null = NULL, or AADFF_PSF_POINTS=raw in the environment is aadff_psf_points_fit / _staged_fit.
+ * Environment, read per launch, for A/B runs and tests: AADFF_PSF_POINTS=raw (above; the prologue then writes no points),
+ * AADFF_CHIEF_CENTRES=per_wavelength (the node rays traced by a wave per (point, wavelength, state) instead of once per (point,
+ * state): the same centres, to the bit), AADFF_PSF_LAUNCHES=parent (both). */
+int aadff_chief_fit_prologue(const float* u_main, int spp, long main_stride_s, long main_stride_l,
+                             const float* u_chief, int S, int L, int spp_chief, long chief_stride_s, long chief_stride_l,
+                             aadff_lens_const_t lc, const aadff_stage_t* stage_or_null, float* weights, float* pupil_xy,
+                             aadff_stream_t stream);
+int aadff_psf_points_fit_pts(const float* points, int S, int N, int L,
+                     const aadff_surface_t* surf_main, const aadff_surface_t* surf_chief,
+                     aadff_lens_const_t lc, const aadff_lens_state_t* states,
+                     const float* u_main, int spp, long main_stride_s, long main_stride_l,
+                     const float* u_chief, int spp_chief, long chief_stride_s, long chief_stride_l,
+                     int ks, int centre_mode, int map_layout, float* psf, float* centre_out_or_null,
+                     int* flags_or_null, const float* fit_weights_or_null, float* fit_centres, const float* pupil_xy_or_null,
+                     aadff_stream_t stream);
+int aadff_psf_points_staged_fit_pts(const float* points, int S, int N, int L,
+                     const aadff_surface_t* surf_main, const aadff_surface_t* surf_chief,
+                     aadff_lens_const_t lc, const aadff_lens_state_t* states,
+                     const float* u_main, int spp, long main_stride_s, long main_stride_l,
+                     const float* u_chief, int spp_chief, long chief_stride_s, long chief_stride_l,
+                     int ks, int centre_mode, int map_layout, float* psf, float* centre_out_or_null,
+                     int* flags_or_null, const aadff_stage_t* stage, const float* fit_weights_or_null, float* fit_centres,
+                     const float* pupil_xy_or_null, aadff_stream_t stream);
 
 /* "Edge-exact" PSF grid (ABI v8; Lensgroup(parity="edge")): aadff_psf_points with the one decision the float32 noise of a trace
  * can flip taken out of the fast kernel.  The histogram's only discontinuity is the window test of deeplens/monte_carlo.py:37
