@@ -4,11 +4,12 @@
 #include <cstdio>
 #include <cstring>
 #include "aadff.h"
+#include "patch_bounds.h"
 
 namespace aadff {
 
 void set_error(const char* fmt, ...);
-// argument domains of the image-space operators (conv.hip, gather.hip), checked the same way by forward and backward entries
+// argument domains of the image-space operators (conv_plan.cpp, gather.hip), checked the same way by forward and backward entries
 int conv_check_shape(int B, int C, int S, int H, int W, int grid, int ks);
 int local_check_shape(int B, int C, int H, int W, int ks);
 
@@ -64,19 +65,7 @@ __device__ __forceinline__ float fresh_uniform(const float* p) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, fresh(p))));
 }
 
-// ------------------------------------------------------------------------------------
-// Patch bounds: Python `int(i / grid * n)` in float64 (deeplens/render_psf.py:65-66).
-// Passed by value in the kernarg segment -> read with scalar loads.
-// ------------------------------------------------------------------------------------
-struct PatchBounds {
-    int hb[AADFF_MAX_GRID + 1];
-    int wb[AADFF_MAX_GRID + 1];
-    // ceil(2^32 / d) for the uniform block-index decompositions: n / d == __umulhi(n, magic) for
-    // n < 65536 (integer division has no scalar form on gfx950 and costs ~15 VALU slots each)
-    unsigned m_ntx, m_nty, m_nchunk, m_c;
-    // XCD-aware block order (xcd_remap): 1-D launches only.  gx, gy = logical grid extents; N = 8 xcd_q + xcd_r blocks (xcd_q = 0: plain order)
-    unsigned gx, gy, xcd_q, xcd_r, m_gx, m_gy;      // m_gx / m_gy != 0: magic multipliers, valid while the launch has < 65536 blocks
-};
+// PatchBounds, magic_of and fill_bounds: patch_bounds.h (plain C++, shared with the host-only conv_plan.cpp)
 
 // Workgroups are dealt round-robin over the 8 XCDs (block b -> XCD b % 8; observed, not promised: speed only), each with an L2 of
 // its own.  Neighbouring bands share halo rows / columns (34 x 108 staged for 24 x 96 rendered: 1.6x), so with the plain order
@@ -88,12 +77,7 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned id, unsigned q, unsigned 
     return k * q + (k < r ? k : r) + j;
 }
 
-__host__ __device__ inline unsigned magic_of(unsigned d) { return (unsigned)((0x100000000ull + d - 1) / d); }
 __device__ __forceinline__ int udiv_magic(unsigned n, unsigned d, unsigned magic) { return d == 1 ? (int)n : (int)__umulhi(n, magic); }
-
-inline void fill_bounds(int* b, int grid, int n) {
-    for (int i = 0; i <= grid; ++i) b[i] = (int)((double)i / (double)grid * (double)n);
-}
 
 __device__ __forceinline__ int reflect_idx(int i, int n) {
     // torch 'reflect' padding (no edge repeat), then clamped: the clamp only matters for

@@ -7,10 +7,12 @@
 #include <type_traits>
 #include <hip/hip_ext.h>
 #include "common.h"
+#include "conv_plan.h"
 
 namespace aadff {
 
-// PatchBounds, fill_bounds, the magic-multiplier divisions, xcd_remap and reflect_idx live in common.h (shared with conv_bwd.hip)
+// PatchBounds, fill_bounds, the magic-multiplier divisions, xcd_remap and reflect_idx live in common.h / patch_bounds.h (shared with
+// conv_bwd.hip); which instantiation a call launches is decided in conv_plan.cpp, the host code at the end of this file only launches it
 
 // ------------------------------------------------------------------------------------
 // Fast path: one wave per 32x32 output tile of ONE patch and ONE channel plane.
@@ -207,9 +209,7 @@ __global__ __launch_bounds__(64 * NW, AADFF_CONV_MINWAVES) void conv_psf_map_ker
 // ds_read_b128 (lane = row l&15, k-group l>>4) bank-conflict free.  B fragments (Toeplitz taps, 8*KS VGPRs) are
 // built once per wave and slice from the 121 taps.
 // ------------------------------------------------------------------------------------
-#ifndef AADFF_MFMA_SPW
-#define AADFF_MFMA_SPW 1          // slices per wave from one staged tile (2 measured slower: 118 vs 74 us)
-#endif
+// (AADFF_MFMA_SPW, slices per wave from one staged tile: conv_plan.h)
 typedef _Float16 half8v __attribute__((ext_vector_type(8)));
 typedef float float4v __attribute__((ext_vector_type(4)));
 
@@ -680,9 +680,6 @@ __device__ __forceinline__ void lds_read16(uint2v& a, uint2v& b, unsigned byte_a
 // Workgroup = one band of RB output rows x 96 columns of one patch and channel plane; wave = one chunk of 4 slices
 // (NC waves).  The band is staged once for all slices (HBM reads the image once), every wave builds the T fragments
 // of its own chunk and walks the band's row pairs.
-#ifndef AADFF_CONV_PAIR_DEFAULT
-#define AADFF_CONV_PAIR_DEFAULT 0      // measured: every pairing is slower than one band per workgroup
-#endif
 // TIMED: the same code under a second name - the launches that carry aadff_time_next_launch's events (bench.py's solo leg) then
 // have their own row in a rocprofv3 --stats summary of the very same command, separate from the launches of the timed region
 // that share the device with the next stack's PSF-grid kernel.
@@ -1595,266 +1592,111 @@ __global__ __launch_bounds__(256) void conv_psf_map_generic_kernel(const float* 
     }
 }
 
-template <int KS>
-static int launch_fast(const float* img, const float* psf, float* out, long sbc, long ss, int B, int C, int S, int H, int W,
-                       int grid, int ntx, int nty, const PatchBounds& pb, hipStream_t st) {
-    // waves per workgroup = slices of one chunk (one slice per wave): least padding, at most 5
-    int nw = 1, best = 1 << 30;
-    const int maxnw = KS == 11 ? 5 : 4;
-    for (int n = maxnw; n >= (S > 1 ? 2 : 1); --n) {      // larger n wins ties; a lone wave per tile only for S == 1
-        if (KS != 11 && n == 3) continue;
-        const int waste = (S + n - 1) / n * n - S;
-        if (waste < best) { best = waste; nw = n; }
-    }
-    const char* env = getenv("AADFF_CONV_NW");                 // tuning override, validated: garbage / out-of-range values are ignored
-    if (env && KS == 11) {
-        const int v = atoi(env);
-        if (v >= 1 && v <= maxnw) nw = v;
-    }
-    const int nchunk = (S + nw - 1) / nw;
-    AADFF_CHECK_ARG((size_t)B * C * nchunk <= 65535, "render_psf_map: B*C*chunks too large");
-    PatchBounds pbm = pb;
-    pbm.m_ntx = magic_of(ntx); pbm.m_nty = magic_of(nty); pbm.m_nchunk = magic_of(nchunk); pbm.m_c = magic_of(C);
-    dim3 g(ntx * grid, nty * grid, B * C * nchunk);
-    // path: "mfma" (Toeplitz GEMM on fp16-split MFMA, KS <= 11) or "valu" (packed fp32 FMA); AADFF_CONV_PATH overrides
-    const char* penv = getenv("AADFF_CONV_PATH");
-    const bool use_mfma = KS <= 11 && !(penv && penv[0] == 'v');
-    if constexpr (KS == 11) {
-        // stacks: slice-batched GEMM (the image is the shared operand); "toeplitz" / "valu" force the older paths
-        if (S >= 3 && !penv) {
-            constexpr int RB = 24;          // band rows (8/12/16/32/48 measured slower)
-            const int nc = S <= 4 ? 1 : (S <= 8 ? 2 : (S <= 12 ? 3 : 4));
-            const int npass = (S + 4 * nc - 1) / (4 * nc);
-            int mh = 0, mw = 0;
-            for (int i = 0; i < grid; ++i) {
-                mh = std::max(mh, pb.hb[i + 1] - pb.hb[i]);
-                mw = std::max(mw, pb.wb[i + 1] - pb.wb[i]);
-            }
-            const int sntx = (mw + sb::TCOLS - 1) / sb::TCOLS, snty = (mh + RB - 1) / RB;
-            AADFF_CHECK_ARG((size_t)B * C * npass <= 65535 && (size_t)snty * grid <= 65535, "render_psf_map: grid too large");
-            AADFF_CHECK_ARG((size_t)H * W <= ((size_t)1 << 27) && 16 * (size_t)ss + 4 * (size_t)H * W < ((size_t)1 << 32),
-                            "render_psf_map: image planes above 2^27 pixels / slice strides above 2^28 elements are not supported on the stack path");
-            // paired bands (default): a workgroup renders two consecutive bands of its patch, the second one prefetched by LDS-DMA
-            // AADFF_CONV_PAIR: 0 = one band per workgroup (round-2 form), N >= 1 = bands in pairs for every N-th (patch, plane)
-            const int pair_mod = [] { const char* e = getenv("AADFF_CONV_PAIR"); const int v = e ? atoi(e) : AADFF_CONV_PAIR_DEFAULT; return v < 0 ? 0 : v; }();   // read per launch: tests switch it
-            const bool pair = pair_mod > 0;
-            const int gny = snty;
-            PatchBounds pbs = pb;
-            pbs.m_ntx = magic_of(sntx); pbs.m_nty = magic_of(gny); pbs.m_nchunk = magic_of(npass); pbs.m_c = magic_of(C);
-            dim3 gs(sntx * grid, gny * grid, B * C * npass);
-            static const int stagger = [] { const char* e = getenv("AADFF_CONV_STAGGER"); const int v = e ? atoi(e) : 1; return v < 0 ? 0 : (v > 64 ? 64 : v); }();   // default 1: -1 % in bench, -7 % back to back
-            // aadff_time_next_launch: the two events ride ON this dispatch (kernel begin / end timestamps)
-            hipEvent_t ev0 = g_time_start, ev1 = g_time_stop;
-            g_time_start = g_time_stop = nullptr;
+
+// ------------------------------------------------------------------------------------
+// Host side.  conv_plan (conv_plan.cpp) decides the instantiation and its launch geometry; conv_launch names the
+// instantiations and launches the one the plan says.  No decision is taken here.
+// ------------------------------------------------------------------------------------
+static_assert(TW == kConvTile && TH == kConvTile && sb::TCOLS == kConvBandCols && blk::TCOLS == kConvBandCols && blk::RB == kConvBlkRows &&
+              blk::NW == kConvBlkWaves, "conv_plan.h restates the kernels' tile sizes");
+
+// out plane of (b, c, s) starts at out + (b*C + c)*sbc + s*ss (elements); the contiguous [B,C,S,H,W] stack is sbc = S*H*W, ss = H*W.
+// ev0 / ev1 (an attaching plan only, or NULL): aadff_time_next_launch's events, which then ride ON the dispatch (kernel begin / end
+// timestamps) of the TIMED twin of the instantiation.
+static int conv_launch(const ConvPlan& pl, const float* img, const float* psf, const unsigned char* layer_idx, float* out, long sbc, long ss,
+                       hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+    const dim3 g(pl.gx, pl.gy, pl.gz), b(pl.block);
+    const int* t = pl.targ;
+    const int C = pl.C, S = pl.S, H = pl.H, W = pl.W, grid = pl.grid, ntx = pl.ntx, nty = pl.nty;
+    bool found = true;
+// (KS, NW) of the packed-FMA and Toeplitz MFMA kernels: 1, 2, 4 waves, ks 11 also 3 and 5
+#define AADFF_NW(K) case K: switch (t[1]) { case 1: AADFF_LAUNCH(K, 1); break; case 2: AADFF_LAUNCH(K, 2); break; case 4: AADFF_LAUNCH(K, 4); break; \
+                                            default: found = false; } break;
+#define AADFF_NW11 case 11: switch (t[1]) { case 1: AADFF_LAUNCH(11, 1); break; case 2: AADFF_LAUNCH(11, 2); break; case 3: AADFF_LAUNCH(11, 3); break; \
+                                            case 4: AADFF_LAUNCH(11, 4); break; case 5: AADFF_LAUNCH(11, 5); break; default: found = false; } break;
+    switch (pl.family) {
+        case ConvFamily::valu:
+#define AADFF_LAUNCH(K, NWV) hipLaunchKernelGGL((conv_psf_map_kernel<K, NWV>), g, b, 0, st, img, psf, out, sbc, ss, C, S, H, W, grid, ntx, nty, pl.pb)
+            switch (t[0]) { AADFF_NW(3) AADFF_NW(5) AADFF_NW(7) AADFF_NW(9) AADFF_NW11 AADFF_NW(13) AADFF_NW(15) AADFF_NW(21) default: found = false; }
+#undef AADFF_LAUNCH
+            break;
+        case ConvFamily::mfma:
+            static_assert(AADFF_MFMA_SPW == 1, "the plan's chunk count and the launch below assume it");
+#define AADFF_LAUNCH(K, NWV) hipLaunchKernelGGL((conv_psf_map_mfma_kernel<K, NWV, AADFF_MFMA_SPW>), g, b, 0, st, img, psf, out, sbc, ss, C, S, H, W, grid, ntx, nty, pl.pb)
+            switch (t[0]) { AADFF_NW(3) AADFF_NW(5) AADFF_NW(7) AADFF_NW(9) AADFF_NW11 default: found = false; }
+#undef AADFF_LAUNCH
+            break;
+        case ConvFamily::generic:
+            hipLaunchKernelGGL(conv_psf_map_generic_kernel, g, b, pl.lds, st, img, psf, out, sbc, ss, C, S, H, W, grid, pl.ks, ntx, nty, pl.pb);
+            break;
+        case ConvFamily::toeplitz_wide: {
+#define AADFF_WIDE(NKV, KSP, MR, MT) if (t[0] == NKV && t[1] == KSP && t[2] == MR && t[3] == MT) \
+            hipLaunchKernelGGL((conv_psf_map_toeplitz_wide_kernel<NKV, KSP, MR, MT>), g, b, pl.lds, st, img, psf, out, sbc, ss, C, S, H, W, grid, pl.ks, pl.P, pl.spw, ntx, nty, pl.pb)
+            AADFF_WIDE(1, true, 12, 2); else AADFF_WIDE(1, false, 12, 5);
+            else AADFF_WIDE(2, true, 13, 2); else AADFF_WIDE(2, false, 13, 7);
+            else AADFF_WIDE(2, true, 16, 4); else AADFF_WIDE(2, false, 16, 16);
+            else AADFF_WIDE(2, true, 20, 10);
+            else AADFF_WIDE(3, true, 21, 11);
+            else found = false;
+#undef AADFF_WIDE
+        } break;
+        case ConvFamily::sbatch: {
+            constexpr int RB = kConvSbRows;
+#define AADFF_SB_ARGS img, psf, out, sbc, ss, C, S, H, W, grid, ntx, nty, pl.nchunk, pl.pb, pl.stagger, pl.pair_mod, layer_idx, pl.L
 #define AADFF_LAUNCH_S3(NCV, PR) do { \
-                if (ev0) hipExtLaunchKernelGGL((conv_psf_map_sbatch_kernel<RB, NCV, PR, true>), gs, dim3(64 * NCV), 0, st, ev0, ev1, 0, img, psf, out, sbc, ss, C, S, H, W, grid, sntx, gny, npass, pbs, stagger, pair_mod, (const unsigned char*)nullptr, 1); \
-                else hipLaunchKernelGGL((conv_psf_map_sbatch_kernel<RB, NCV, PR, false>), gs, dim3(64 * NCV), 0, st, img, psf, out, sbc, ss, C, S, H, W, grid, sntx, gny, npass, pbs, stagger, pair_mod, (const unsigned char*)nullptr, 1); } while (0)
-#define AADFF_LAUNCH_S(NCV) do { if (pair) AADFF_LAUNCH_S3(NCV, true); else AADFF_LAUNCH_S3(NCV, false); } while (0)
-            switch (nc) {
-                case 1: AADFF_LAUNCH_S(1); break;
-                case 2: AADFF_LAUNCH_S(2); break;
-                case 3: AADFF_LAUNCH_S(3); break;
-                default: AADFF_LAUNCH_S(4);
-            }
+                if (ev0) hipExtLaunchKernelGGL((conv_psf_map_sbatch_kernel<RB, NCV, PR, true>), g, b, 0, st, ev0, ev1, 0, AADFF_SB_ARGS); \
+                else hipLaunchKernelGGL((conv_psf_map_sbatch_kernel<RB, NCV, PR, false>), g, b, 0, st, AADFF_SB_ARGS); } while (0)
+#define AADFF_LAUNCH_S(NCV) case NCV: if (t[4]) hipLaunchKernelGGL((conv_psf_map_sbatch_kernel<RB, NCV, false, false, true>), g, b, 0, st, AADFF_SB_ARGS); \
+                                      else if (t[2]) AADFF_LAUNCH_S3(NCV, true); else AADFF_LAUNCH_S3(NCV, false); break;
+            if (t[0] != RB) found = false;
+            else switch (t[1]) { AADFF_LAUNCH_S(1) AADFF_LAUNCH_S(2) AADFF_LAUNCH_S(3) AADFF_LAUNCH_S(4) default: found = false; }
 #undef AADFF_LAUNCH_S
 #undef AADFF_LAUNCH_S3
-            return 0;
-        }
-    }
-    if constexpr (KS == 9 || KS == 11) {
-        // lone slices (render_psf_map / render_psf as the reference calls them) and pairs: block-GEMM form, 21 instead of 33
-        // MFMAs per 256 outputs and the slice-batched kernel's staging; AADFF_CONV_PATH = toeplitz / valu force the older paths
-        // S == 1 only - measured (tools/conv_paths_bench.py, 1024^2, us): ks 11: S = 1 14.5-16.6 against 19.3-19.8 Toeplitz, S = 2
-        // 23.2 / 23.0 (re-staging per slice cancels the gain; a form that renders three slices from one staged band was built
-        // and was no faster: 23.0 / 28.9 for S = 2 / 3); ks 9: S = 1 14.5 / 18.5, S = 2 23.8 / 21.0, S = 10 86 / 72-78
-        if (S == 1 && B * C <= 65535 && !penv && (size_t)H * W <= ((size_t)1 << 30)) {
-            int mh = 0, mw = 0;
-            for (int i = 0; i < grid; ++i) {
-                mh = std::max(mh, pb.hb[i + 1] - pb.hb[i]);
-                mw = std::max(mw, pb.wb[i + 1] - pb.wb[i]);
-            }
-            const int bntx = (mw + blk::TCOLS - 1) / blk::TCOLS, bnty = (mh + blk::RB - 1) / blk::RB;
-            const size_t gx = (size_t)bntx * grid, gy = (size_t)bnty * grid, total = gx * gy * B * C * S;
-            if (total < ((size_t)1 << 31)) {
-                PatchBounds pbb = pb;
-                pbb.m_ntx = magic_of(bntx); pbb.m_nty = magic_of(bnty); pbb.m_nchunk = magic_of(S); pbb.m_c = magic_of(C);
-                pbb.gx = (unsigned)gx; pbb.gy = (unsigned)gy;
-                const bool magic = total < 65536;
-                pbb.m_gx = magic ? (gx == 1 ? 1u : magic_of((unsigned)gx)) : 0u;           // (udiv_magic returns n for d == 1; the flag is m_gx != 0)
-                pbb.m_gy = magic ? (gy == 1 ? 1u : magic_of((unsigned)gy)) : 0u;
-                pbb.xcd_q = total >= 64 ? (unsigned)(total / 8) : 0u;
-                pbb.xcd_r = (unsigned)(total % 8);
-                hipLaunchKernelGGL((conv_psf_map_blk_kernel<KS>), dim3((unsigned)total), dim3(64 * blk::NW), 0, st, img, psf, out, sbc, ss, C, S, H, W, grid, bntx, bnty, pbb);
-                return 0;
-            }
-        }
-    }
-    if constexpr (KS <= 11) {
-        if (use_mfma) {
-            const int nchunk_m = (S + nw * AADFF_MFMA_SPW - 1) / (nw * AADFF_MFMA_SPW);
-            dim3 gm(ntx * grid, nty * grid, B * C * nchunk_m);
-            PatchBounds pbmm = pbm;
-            pbmm.m_nchunk = magic_of(nchunk_m);
-#define AADFF_LAUNCH_M(NWV) hipLaunchKernelGGL((conv_psf_map_mfma_kernel<KS, NWV, AADFF_MFMA_SPW>), gm, dim3(64 * NWV), 0, st, img, psf, out, sbc, ss, C, S, H, W, grid, ntx, nty, pbmm)
-            switch (nw) {
-                case 5: if constexpr (KS == 11) { AADFF_LAUNCH_M(5); break; }
-                case 4: AADFF_LAUNCH_M(4); break;
-                case 3: if constexpr (KS == 11) { AADFF_LAUNCH_M(3); break; }
-                case 2: AADFF_LAUNCH_M(2); break;
-                default: AADFF_LAUNCH_M(1);
-            }
-#undef AADFF_LAUNCH_M
-            return 0;
-        }
-    }
-#define AADFF_LAUNCH(NWV) hipLaunchKernelGGL((conv_psf_map_kernel<KS, NWV>), g, dim3(64 * NWV), 0, st, img, psf, out, sbc, ss, C, S, H, W, grid, ntx, nty, pbm)
-    if constexpr (KS == 11) {
-        switch (nw) {
-            case 5: AADFF_LAUNCH(5); break;
-            case 4: AADFF_LAUNCH(4); break;
-            case 3: AADFF_LAUNCH(3); break;
-            case 2: AADFF_LAUNCH(2); break;
-            default: AADFF_LAUNCH(1);
-        }
-    } else {
-        switch (nw) {
-            case 4: AADFF_LAUNCH(4); break;
-            case 2: AADFF_LAUNCH(2); break;
-            default: AADFF_LAUNCH(1);
-        }
-    }
-#undef AADFF_LAUNCH
-    return 0;
-}
-
-// the shape domain of the patch convolution, shared by the forward entries and their backward (conv_bwd.hip)
-int conv_check_shape(int B, int C, int S, int H, int W, int grid, int ks) {
-    AADFF_CHECK_ARG(B > 0 && C > 0 && S > 0 && H > 0 && W > 0, "render_psf_map: empty tensor (B=%d C=%d S=%d H=%d W=%d)", B, C, S, H, W);
-    AADFF_CHECK_ARG(grid >= 1 && grid <= AADFF_MAX_GRID, "render_psf_map: grid %d outside [1,%d]", grid, AADFF_MAX_GRID);
-    AADFF_CHECK_ARG(ks % 2 == 1, "PSF kernel size should be odd");
-    AADFF_CHECK_ARG(ks >= 1 && ks <= AADFF_MAX_KS, "render_psf_map: ks %d outside [1,%d]", ks, AADFF_MAX_KS);
-    AADFF_CHECK_ARG(ks / 2 < H && ks / 2 < W, "render_psf_map: reflect padding %d needs H,W > pad", ks / 2);
-    AADFF_CHECK_ARG(grid <= H && grid <= W, "render_psf_map: grid %d larger than image %dx%d", grid, H, W);
-    AADFF_CHECK_ARG((size_t)B * C <= 65535, "render_psf_map: B*C too large");
-    return 0;
-}
-
-// out plane of (b, c, s) starts at out + (b*C + c)*sbc + s*ss (elements); the contiguous [B,C,S,H,W] stack is sbc = S*H*W, ss = H*W
-static int conv_dispatch(const float* img, const float* psf, float* out, long sbc, long ss, int B, int C, int S, int H, int W,
-                         int grid, int ks, hipStream_t st) {
-    AADFF_CHECK_ARG(img && psf && out, "render_psf_map: NULL pointer");
-    if (int rc = conv_check_shape(B, C, S, H, W, grid, ks)) return rc;
-
-    PatchBounds pb;
-    std::memset(&pb, 0, sizeof(pb));
-    fill_bounds(pb.hb, grid, H);
-    fill_bounds(pb.wb, grid, W);
-    int mh = 0, mw = 0;
-    for (int i = 0; i < grid; ++i) {
-        mh = std::max(mh, pb.hb[i + 1] - pb.hb[i]);
-        mw = std::max(mw, pb.wb[i + 1] - pb.wb[i]);
-    }
-    const int ntx = (mw + TW - 1) / TW, nty = (mh + TH - 1) / TH;
-    if (ks >= 3 && ks <= 21 && !getenv("AADFF_CONV_PATH")) {
-        // block-GEMM form (conv_psf_map_blkw_kernel): AADFF_CONV_BLKW = 0 never, 1 always, unset: where it measured faster
-        // (tools/conv_blkw_probe.py -> profiles/r05_y_conv_blkw_probe.txt, 1024^2, us per launch blkw / wide Toeplitz / packed-FMA -
-        // lone slices at grid 7: ks 13 15.0 / 31.6 / 30.8, ks 15 22.3 / 32.0 / 41.3, ks 17 21.4 / 33.5 / 94.8, ks 19 30.7 / 41.4 / 110.5,
-        // ks 21 27.3 / 43.6 / 79.8 (grid 11: 24.3 / 38.7 / 80.4); 10-slice stacks (one workgroup per slice and band here, the Toeplitz
-        // form shares its staged tile between four slices) at grid 7 / 11: ks 13 105 / 113 and 78 / 105, ks 15 156 / 124 and 113 / 109,
-        // ks 17 134 / 131 and 100 / 124, ks 19 291 / 247 and 198 / 217, ks 21 224 / 270 and 158 / 237)
-        const char* benv = getenv("AADFF_CONV_BLKW");
-        const int blkw = benv ? atoi(benv) : -1;
-        // ks 9 / 11 lone slices (us, conv_psf_map_blk_kernel / this kernel with 24- / 32- / 48-row bands; ks 9's window here is 12 x 12 =
-        // 5 k-steps, the older kernel's fixed 14 x 14 = 7): ks 9 grid 7 16.3 / 13.0 / 12.1 / 13.2, grid 11 12.9 / 11.1 / 11.4 / 12.0, grid 5
-        // 15.1 / 11.7 / 12.1 / 12.8; ks 11 grid 7 15.4 / 15.9 / 13.2 / 14.9, grid 11 12.3 / 12.9 / 13.4 / 12.9, grid 5 14.8 / 15.7 / 14.0 / 14.7
-        // ks 3 / 5 / 7 (window ks + 3: 2 / 2 / 4 k-steps; the Toeplitz kernel (b) issues 3 ks MFMAs per 16 x 16 block, this form 3 NST per
-        // 16 x 16): lone slices 9 - 12 us against 13 - 17 at every grid, 10-slice stacks faster at ks 5 only (grid 7 / 11: 53 / 47 against 62 / 54)
-        const bool use = blkw == 1 || (blkw == -1 && (ks >= 13 ? (S == 1 || ks == 13 || ks == 17 || ks == 21)
-                                                                : (S == 1 ? (ks <= 9 || mh > 96) : ks == 5)));
-        // rows per band: every workgroup pays ~5.5 us of loads / staging / fragment building in front of 0.76 us of matrix work per
-        // 8-row group (tools/conv_single_timeline.py --ks 21: profiles/r05_y_conv_blkw_timeline_ks21.json), so taller bands win until the
-        // launch is too few workgroups for two rounds on 512 slots.  Measured at 1024^2 (ks 21, us, RB 24 / 32 / 48): grid 7 (147-row
-        // patches) 32.4 / 27.8 / 30.6, grid 11 (94) 25.2 / 25.3 / 24.2, grid 5 (205) 29.1 / 26.8 / 25.4; the other ks alike.
-        const char* renv = getenv("AADFF_CONV_BLKW_RB");
-        int rb = renv ? atoi(renv) : 0;
-        if (rb != 24 && rb != 32 && rb != 48) {
-            if (ks <= 11) {
-                // 6 workgroups per CU: 32-row bands when that saves a round of workgroups on the chip's 1536 slots (1024^2: grid 7 yes,
-                // grid 5 / 11 no - measured, ks 5: 9.4 / 9.1, 9.2 / 9.7, 8.7 / 8.9 us with 24 / 32 rows)
-                const size_t per = (size_t)((mw + 95) / 96) * grid * grid * B * C * S;
-                const size_t w24 = per * ((mh + 23) / 24), w32 = per * ((mh + 31) / 32);
-                rb = (w24 + 1535) / 1536 > (w32 + 1535) / 1536 ? 32 : 24;
-            } else rb = mh <= 24 ? 24 : (mh <= 32 ? 32 : (mh <= 48 ? 48 : (mh <= 64 ? 32 : (mh <= 96 ? 48 : 32))));
-        }
-        const int bntx = (mw + 96 - 1) / 96, bnty = (mh + rb - 1) / rb;
-        const size_t gx = (size_t)bntx * grid, gy = (size_t)bnty * grid, total = gx * gy * B * C * S;
-        if (use && total < ((size_t)1 << 31) && (size_t)H * W <= ((size_t)1 << 30)) {
-            PatchBounds pbb = pb;
-            pbb.m_ntx = magic_of(bntx); pbb.m_nty = magic_of(bnty); pbb.m_nchunk = magic_of(S); pbb.m_c = magic_of(C);
-            pbb.gx = (unsigned)gx; pbb.gy = (unsigned)gy;
-            const bool magic = total < 65536;
-            pbb.m_gx = magic ? (gx == 1 ? 1u : magic_of((unsigned)gx)) : 0u;
-            pbb.m_gy = magic ? (gy == 1 ? 1u : magic_of((unsigned)gy)) : 0u;
-            pbb.xcd_q = total >= 64 ? (unsigned)(total / 8) : 0u;
-            pbb.xcd_r = (unsigned)(total % 8);
-#define AADFF_BLKW2(K, R) hipLaunchKernelGGL((conv_psf_map_blkw_kernel<K, R>), dim3((unsigned)total), dim3(192), 0, st, img, psf, out, sbc, ss, C, S, H, W, grid, bntx, bnty, pbb)
-#define AADFF_BLKW(K) case K: if (rb == 24) AADFF_BLKW2(K, 24); else if (rb == 32) AADFF_BLKW2(K, 32); else AADFF_BLKW2(K, 48); break;
-            switch (ks) { AADFF_BLKW(3) AADFF_BLKW(5) AADFF_BLKW(7) AADFF_BLKW(9) AADFF_BLKW(11) AADFF_BLKW(13) AADFF_BLKW(15) AADFF_BLKW(17) AADFF_BLKW(19) AADFF_BLKW(21) }
+#undef AADFF_SB_ARGS
+        } break;
+        case ConvFamily::blk:
+#define AADFF_BLK(K) case K: hipLaunchKernelGGL((conv_psf_map_blk_kernel<K>), g, b, 0, st, img, psf, out, sbc, ss, C, S, H, W, grid, ntx, nty, pl.pb); break;
+            switch (t[0]) { AADFF_BLK(9) AADFF_BLK(11) default: found = false; }
+#undef AADFF_BLK
+            break;
+        case ConvFamily::blkw:
+#define AADFF_BLKW2(K, R) hipLaunchKernelGGL((conv_psf_map_blkw_kernel<K, R>), g, b, 0, st, img, psf, out, sbc, ss, C, S, H, W, grid, ntx, nty, pl.pb)
+#define AADFF_BLKW(K) case K: if (t[1] == 24) AADFF_BLKW2(K, 24); else if (t[1] == 32) AADFF_BLKW2(K, 32); else if (t[1] == 48) AADFF_BLKW2(K, 48); else found = false; break;
+            switch (t[0]) { AADFF_BLKW(3) AADFF_BLKW(5) AADFF_BLKW(7) AADFF_BLKW(9) AADFF_BLKW(11) AADFF_BLKW(13) AADFF_BLKW(15) AADFF_BLKW(17) AADFF_BLKW(19) AADFF_BLKW(21)
+                            default: found = false; }
 #undef AADFF_BLKW
 #undef AADFF_BLKW2
-            AADFF_CHECK_LAUNCH();
-            return 0;
-        }
+            break;
     }
-    if (ks >= 13 && !getenv("AADFF_CONV_PATH")) {
-        // large kernels on the matrix cores (Toeplitz GEMM over NK k-steps); AADFF_CONV_PATH=valu keeps the packed-FMA / generic kernels
-        const int nk = (16 + ks - 1 + 31) / 32;                         // 1: ks <= 17, 2: ks <= 49, 3: ks 51
-        const int twp = TW + ks - 1, thp = TH + ks - 1;
-        int P = (twp + 7) / 8 * 8;
-        while (P % 16 != 8) P += 8;                                      // P / 2 dwords = 4 (mod 8): conflict-free A-fragment reads
-        if (P < 32 * nk + 16 + 8) P = 32 * nk + 24;                      // the last k-step's 8 halves stay inside the row (zero padding)
-        while (P % 16 != 8) P += 8;
-        const size_t tile_b = (size_t)2 * thp * P * sizeof(_Float16), rows_b = (size_t)ks * 2 * (32 * nk + 18) * sizeof(_Float16);
-        // waves = slices when four tap-row sets fit beside the tile and there are slices to share it; else the waves split the tap rows
-        const bool ksplit = S < 2 || tile_b + 4 * rows_b > 64 * 1024 - 64 || ks > 31;
-        const size_t lds = tile_b + (ksplit ? std::max(rows_b, (size_t)16384) : 4 * rows_b);
-        AADFF_CHECK_ARG(lds <= 64 * 1024 - 64, "render_psf_map: ks %d needs %zu bytes of LDS", ks, lds);
-        // slices per workgroup: the whole stack from one staged tile unless that leaves the chip short of workgroups
-        const long tiles = (long)ntx * grid * nty * grid * B * C;
-        int spw = S;
-        while (spw > (ksplit ? 1 : 4) && tiles * ((S + spw - 1) / spw) < 2048) spw = (spw + 1) / 2;
-        if (!ksplit) spw = (spw + 3) / 4 * 4;
-        const int nchunk = (S + spw - 1) / spw;
-        AADFF_CHECK_ARG((size_t)B * C * nchunk <= 65535, "render_psf_map: B*C*chunks too large");
-        PatchBounds pbm = pb;
-        pbm.m_ntx = magic_of(ntx); pbm.m_nty = magic_of(nty); pbm.m_nchunk = magic_of(nchunk); pbm.m_c = magic_of(C);
-        dim3 g(ntx * grid, nty * grid, B * C * nchunk);
-#define AADFF_WIDE(NKV, KSP, MR, MT) hipLaunchKernelGGL((conv_psf_map_toeplitz_wide_kernel<NKV, KSP, MR, MT>), g, dim3(256), lds, st, img, psf, out, sbc, ss, C, S, H, \
-                                                        W, grid, ks, P, spw, ntx, nty, pbm)
-        // size classes: rows per thread = ceil((32 + ks - 1) / 4), taps per thread = ceil(ks^2 / 256) (tap rows split) or / 64 (slices split)
-        if (ks <= 17) { if (ksplit) AADFF_WIDE(1, true, 12, 2); else AADFF_WIDE(1, false, 12, 5); }
-        else if (ks <= 21) { if (ksplit) AADFF_WIDE(2, true, 13, 2); else AADFF_WIDE(2, false, 13, 7); }
-        else if (ks <= 31) { if (ksplit) AADFF_WIDE(2, true, 16, 4); else AADFF_WIDE(2, false, 16, 16); }
-        else if (ks <= 49) AADFF_WIDE(2, true, 20, 10);
-        else AADFF_WIDE(3, true, 21, 11);
-#undef AADFF_WIDE
-        AADFF_CHECK_LAUNCH();
-        return 0;
-    }
-    switch (ks) {
-#define AADFF_CASE(K) case K: { int rc = launch_fast<K>(img, psf, out, sbc, ss, B, C, S, H, W, grid, ntx, nty, pb, st); if (rc) return rc; } break;
-        AADFF_CASE(3) AADFF_CASE(5) AADFF_CASE(7) AADFF_CASE(9) AADFF_CASE(11) AADFF_CASE(13)
-        AADFF_CASE(15) AADFF_CASE(21)
-#undef AADFF_CASE
-        default: {
-            dim3 g(ntx * grid, nty * grid, B * C);
-            const size_t lds = ((size_t)(TH + ks - 1) * (TW + ks - 1) + (size_t)ks * ks) * sizeof(float);
-            hipLaunchKernelGGL(conv_psf_map_generic_kernel, g, dim3(256), lds, st, img, psf, out, sbc, ss, C, S, H, W, grid,
-                               ks, ntx, nty, pb);
-        }
+#undef AADFF_NW
+#undef AADFF_NW11
+    if (!found) {                                                // a plan that names a kernel this unit does not hold: a bug, never a fall-back
+        char name[96];
+        conv_plan_name(pl, name, sizeof(name));
+        set_error("render_psf_map: no instantiation %s", name);
+        return AADFF_EUNSUPPORTED;
     }
     AADFF_CHECK_LAUNCH();
     return 0;
+}
+
+// One call of an entry: plan, then launch.  The stack entries honour aadff_time_next_launch: an attaching plan carries the events on
+// its dispatch, every other one is bracketed by them; the call consumes the arming whether it launches or refuses.
+static int conv_run(ConvEntry entry, const float* img, const float* psf, const unsigned char* layer_idx, float* out, long sbc, long ss,
+                    int B, int C, int S, int L, int H, int W, int grid, int ks, hipStream_t st) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (entry != ConvEntry::map && entry != ConvEntry::psf) {
+        e0 = g_time_start; e1 = g_time_stop;
+        g_time_start = g_time_stop = nullptr;
+    }
+    ConvPlan pl;
+    const bool ptrs_ok = img && psf && out && (entry != ConvEntry::layered || layer_idx);
+    if (int rc = conv_plan(pl, entry, ptrs_ok, B, C, S, L, H, W, grid, ks, sbc, ss)) return rc;
+    const bool bracket = e0 && !pl.attach;
+    if (bracket) AADFF_CHECK_HIP(hipEventRecord(e0, st));
+    const int rc = conv_launch(pl, img, psf, layer_idx, out, sbc, ss, st, pl.attach ? e0 : nullptr, e1);
+    if (bracket && rc == 0) AADFF_CHECK_HIP(hipEventRecord(e1, st));
+    return rc;
 }
 
 }  // namespace aadff
@@ -1865,86 +1707,22 @@ extern "C" {
 
 int aadff_render_psf_map(const float* img, const float* psf_map, float* out, int B, int C, int H, int W, int grid,
                          int ks, aadff_stream_t stream) {
-    return conv_dispatch(img, psf_map, out, (long)H * W, (long)H * W, B, C, 1, H, W, grid, ks, (hipStream_t)stream);
-}
-
-static int stack_launch(const float* img, const float* psf_maps, float* out, long sbc, long ss, int B, int C, int S, int H,
-                        int W, int grid, int ks, hipStream_t st) {
-    hipEvent_t e0 = g_time_start, e1 = g_time_stop;
-    // armed by aadff_time_next_launch: the slice-batched launch attaches the events to its dispatch; every other path
-    // records them around the call
-    const bool bracket = e0 && !(ks == 11 && S >= 3 && !getenv("AADFF_CONV_PATH"));
-    if (bracket) {
-        g_time_start = g_time_stop = nullptr;
-        AADFF_CHECK_HIP(hipEventRecord(e0, st));
-    }
-    const int rc = conv_dispatch(img, psf_maps, out, sbc, ss, B, C, S, H, W, grid, ks, st);
-    g_time_start = g_time_stop = nullptr;
-    if (bracket && rc == 0) AADFF_CHECK_HIP(hipEventRecord(e1, st));
-    return rc;
+    return conv_run(ConvEntry::map, img, psf_map, nullptr, out, (long)H * W, (long)H * W, B, C, 1, 1, H, W, grid, ks, (hipStream_t)stream);
 }
 
 int aadff_render_psf_map_stack(const float* img, const float* psf_maps, float* out, int B, int C, int S, int H,
                                int W, int grid, int ks, aadff_stream_t stream) {
-    return stack_launch(img, psf_maps, out, (long)S * H * W, (long)H * W, B, C, S, H, W, grid, ks, (hipStream_t)stream);
+    return conv_run(ConvEntry::stack, img, psf_maps, nullptr, out, (long)S * H * W, (long)H * W, B, C, S, 1, H, W, grid, ks, (hipStream_t)stream);
 }
 
 int aadff_render_psf_map_stack_layered(const float* img, const float* psf_maps, const unsigned char* layer_idx, float* out, int B, int C, int S,
                                        int L, int H, int W, int grid, int ks, aadff_stream_t stream) {
-    AADFF_CHECK_ARG(img && psf_maps && layer_idx && out, "render_psf_map_stack_layered: NULL pointer");
-    AADFF_CHECK_ARG(B > 0 && C > 0 && S > 0 && L >= 1 && L <= 254 && H > 0 && W > 0, "render_psf_map_stack_layered: B=%d C=%d S=%d L=%d H=%d W=%d", B, C, S, L, H, W);
-    AADFF_CHECK_ARG(grid >= 1 && grid <= AADFF_MAX_GRID && grid <= H && grid <= W, "render_psf_map_stack_layered: grid %d", grid);
-    if (ks != 11) {
-        set_error("render_psf_map_stack_layered: the fused form exists for ks 11 only (ks %d: compose aadff_render_psf_map_stack and a gather)", ks);
-        return AADFF_EUNSUPPORTED;
-    }
-    AADFF_CHECK_ARG(5 < H && 5 < W, "render_psf_map_stack_layered: reflect padding 5 needs H,W > pad");
-    const long ss = (long)H * W, sbc = (long)S * ss;
-    const int maps = S * L;
-    PatchBounds pb;
-    std::memset(&pb, 0, sizeof(pb));
-    fill_bounds(pb.hb, grid, H);
-    fill_bounds(pb.wb, grid, W);
-    int mh = 0, mw = 0;
-    for (int i = 0; i < grid; ++i) {
-        mh = std::max(mh, pb.hb[i + 1] - pb.hb[i]);
-        mw = std::max(mw, pb.wb[i + 1] - pb.wb[i]);
-    }
-    constexpr int RB = 24;
-    const int nc = maps <= 4 ? 1 : (maps <= 8 ? 2 : (maps <= 12 ? 3 : 4));
-    const int npass = (maps + 4 * nc - 1) / (4 * nc);
-    const int sntx = (mw + sb::TCOLS - 1) / sb::TCOLS, snty = (mh + RB - 1) / RB;
-    AADFF_CHECK_ARG((size_t)B * C * npass <= 65535 && (size_t)snty * grid <= 65535, "render_psf_map_stack_layered: grid too large");
-    AADFF_CHECK_ARG((size_t)H * W <= ((size_t)1 << 27) && 4 * ((size_t)S * ss + (size_t)H * W) < ((size_t)1 << 32),
-                    "render_psf_map_stack_layered: a (b, c) plane stack above 2^30 elements is not supported");
-    pb.m_ntx = magic_of(sntx); pb.m_nty = magic_of(snty); pb.m_nchunk = magic_of(npass); pb.m_c = magic_of(C);
-    dim3 gs(sntx * grid, snty * grid, B * C * npass);
-    hipStream_t st = (hipStream_t)stream;
-    hipEvent_t e0 = g_time_start, e1 = g_time_stop;                             // aadff_time_next_launch: bracket this launch
-    g_time_start = g_time_stop = nullptr;
-    if (e0) AADFF_CHECK_HIP(hipEventRecord(e0, st));
-#define AADFF_LAUNCH_L(NCV) hipLaunchKernelGGL((conv_psf_map_sbatch_kernel<RB, NCV, false, false, true>), gs, dim3(64 * NCV), 0, st, img, psf_maps, out, sbc, ss, C, \
-                                               maps, H, W, grid, sntx, snty, npass, pb, 0, 0, layer_idx, L)
-    switch (nc) {
-        case 1: AADFF_LAUNCH_L(1); break;
-        case 2: AADFF_LAUNCH_L(2); break;
-        case 3: AADFF_LAUNCH_L(3); break;
-        default: AADFF_LAUNCH_L(4);
-    }
-#undef AADFF_LAUNCH_L
-    if (e0) AADFF_CHECK_HIP(hipEventRecord(e1, st));
-    AADFF_CHECK_LAUNCH();
-    return 0;
+    return conv_run(ConvEntry::layered, img, psf_maps, layer_idx, out, (long)S * H * W, (long)H * W, B, C, S, L, H, W, grid, ks, (hipStream_t)stream);
 }
 
 int aadff_render_psf_map_stack_strided(const float* img, const float* psf_maps, float* out, long stride_bc, long stride_s,
                                        int B, int C, int S, int H, int W, int grid, int ks, aadff_stream_t stream) {
-    AADFF_CHECK_ARG(stride_bc >= (long)H * W && stride_s >= (long)H * W, "render_psf_map_stack_strided: strides %ld / %ld below one plane (%d x %d)",
-                    stride_bc, stride_s, H, W);
-    // the S*B*C planes must not overlap: either slices are innermost (stride_bc >= S*stride_s) or (b, c) planes are (stride_s >= B*C*stride_bc)
-    AADFF_CHECK_ARG(stride_bc >= (long)S * stride_s || stride_s >= (long)B * C * stride_bc,
-                    "render_psf_map_stack_strided: planes overlap (stride_bc %ld, stride_s %ld, B*C %d, S %d)", stride_bc, stride_s, B * C, S);
-    return stack_launch(img, psf_maps, out, stride_bc, stride_s, B, C, S, H, W, grid, ks, (hipStream_t)stream);
+    return conv_run(ConvEntry::strided, img, psf_maps, nullptr, out, stride_bc, stride_s, B, C, S, 1, H, W, grid, ks, (hipStream_t)stream);
 }
 
 #ifdef AADFF_SB_TRACE
@@ -1957,7 +1735,7 @@ extern "C" int aadff_sb_trace_buffer(unsigned long long* dev_buf) {      // not 
 int aadff_render_psf(const float* img, const float* psf, float* out, int B, int C, int H, int W, int ks,
                      aadff_stream_t stream) {
     // a 1x1 PSF grid: the [C,ks,ks] PSF is its own map (render_psf.py:12-28 vs :31-73)
-    return conv_dispatch(img, psf, out, (long)H * W, (long)H * W, B, C, 1, H, W, 1, ks, (hipStream_t)stream);
+    return conv_run(ConvEntry::psf, img, psf, nullptr, out, (long)H * W, (long)H * W, B, C, 1, 1, H, W, 1, ks, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -163,13 +163,25 @@ int aadff_render_psf_map_blend_stack(const float* img, const float* psf_maps, fl
  * or aadff_psf_points / aadff_psf_points_staged call made by this host thread so that its kernel is launched with the two
  * HIP events (hipEvent_t, timing enabled) attached to the dispatch (hipExtLaunchKernelGGL): hipEventElapsedTime then gives
  * the kernel's own begin-to-end time - what rocprofv3 reports - instead of the bracket of two stream events, which adds the
- * dispatch gaps (~2-4 us).  NULL, NULL disarms.  Other launches ignore it. */
+ * dispatch gaps (~2-4 us).  A stack call (plain, strided or layered) that launches any other convolution kernel records the two
+ * events around its launch instead; a stack call that refuses its arguments disarms.  NULL, NULL disarms.  Other launches ignore it. */
 int aadff_time_next_launch(void* start_event, void* stop_event);
 
 /* One PSF for the whole image.  Replaces render_psf, deeplens/render_psf.py:12-28.
  * psf [C,ks,ks]. */
 int aadff_render_psf(const float* img, const float* psf, float* out,
                      int B, int C, int H, int W, int ks, aadff_stream_t stream);
+
+/* Diagnostics: what the patch-convolution entry `entry` ("map": aadff_render_psf_map, "psf": aadff_render_psf, "stack", "strided",
+ * "layered": the aadff_render_psf_map_stack* entries) would launch for these arguments under the current environment (the
+ * AADFF_CONV_* switches).  Host arithmetic only: the very plan the entry launches from, no device is touched.  S is ignored by
+ * "map" / "psf" (one slice), grid by "psf" (1), L by all but "layered", the strides by all but "strided".
+ * name [name_len]: the kernel instantiation as the library's symbol table spells it (nm -C), e.g. conv_psf_map_blkw_kernel<13, 32>;
+ * info [5]: workgroups, threads per workgroup, dynamic LDS bytes, slices per workgroup of a wide Toeplitz launch (0 otherwise),
+ * 1 if the launch takes aadff_time_next_launch's events on its own dispatch (0: they are recorded around it).
+ * A shape the entry refuses returns the entry's own code and sets its message. */
+int aadff_conv_plan_describe(const char* entry, int B, int C, int S, int L, int H, int W, int grid, int ks, long stride_bc,
+                             long stride_s, char* name, int name_len, long long* info);
 
 /* Per-pixel PSF gather (no flip, replicate padding, same PSF for every channel).
  * Replaces local_psf_render, deeplens/render_psf.py:76-107.  psf [B,H,W,ks,ks]. */

@@ -1,6 +1,7 @@
 """Shared by tests/test_conv_paths_host.py and tests/test_gpu_conv_paths.py (not a test module): the case table, the inputs, the comparators
 and the budgets of the forward tests of the patch convolution (aadff_render_psf_map and its stack / strided / layered / uniform-PSF
-entries, csrc/conv.hip), one case for every kernel instantiation the dispatch can reach.
+entries, csrc/conv.hip), one case for every kernel instantiation the dispatch can reach.  The rule that picks the instantiation lives in
+csrc/conv_plan.cpp (conv_plan); `dispatch` below restates it independently, and the host module holds the library to the restatement.
 
 Comparator: oracle.conv.render_psf_map on .double() inputs, slice by slice (`loop64` anchors it on tiny cases).
 
@@ -64,8 +65,8 @@ def _bounds(n, grid):
 
 
 def dispatch(c):
-    """The instantiation conv_dispatch / launch_fast / aadff_render_psf_map_stack_layered (csrc/conv.hip) launch for a case: name as the
-    library's symbol table spells it, family."""
+    """The instantiation the library launches for a case: name as the library's symbol table spells it, family.  An independent statement
+    of the rule of conv_plan (csrc/conv_plan.cpp); tests/test_conv_paths_host.py compares the two through aadff_conv_plan_describe."""
     env, ks, S = c.env, c.ks, c.S
     hb, wb = _bounds(c.H, c.grid), _bounds(c.W, c.grid)
     mh, mw = max(b - a for a, b in zip(hb, hb[1:])), max(b - a for a, b in zip(wb, wb[1:]))
@@ -145,7 +146,7 @@ def _atoi(s, default):
 
 
 def toeplitz_slices_per_workgroup(c):
-    """spw of the wide Toeplitz launch (conv_dispatch): the slices one workgroup renders from its staged tile."""
+    """spw of the wide Toeplitz launch (conv_plan): the slices one workgroup renders from its staged tile."""
     hb, wb = _bounds(c.H, c.grid), _bounds(c.W, c.grid)
     mh, mw = max(b - a for a, b in zip(hb, hb[1:])), max(b - a for a, b in zip(wb, wb[1:]))
     ksplit = "true" in dispatch(c)[0]

@@ -2,10 +2,12 @@
 _generic_kernel, _mfma_kernel, _toeplitz_wide_kernel, _sbatch_kernel, _blk_kernel, _blkw_kernel) that an argument or a switch can reach,
 against float64 on the CPU.
 
-tests/conv_paths_common.py has the case table (each case built for one instantiation, named by `dispatch`, the restated rules of
-conv_dispatch / launch_fast), the comparator (oracle.conv.render_psf_map in float64, slice by slice) and the derived bounds;
-tests/test_conv_paths_host.py shows on the CPU that the bounds are attainable and reject planted errors, and that the table reaches all
-96 instantiations that are not TIMED.  profiles/conv_paths_coverage.md is the kernel trace of this module.  Every case asserts
+tests/conv_paths_common.py has the case table (each case built for one instantiation, named by `dispatch`, an independent restatement
+of the rule of conv_plan, csrc/conv_plan.cpp), the comparator (oracle.conv.render_psf_map in float64, slice by slice) and the derived
+bounds; tests/test_conv_paths_host.py shows on the CPU that the bounds are attainable and reject planted errors, that the table reaches
+all 96 instantiations that are not TIMED, and that the library's own plan (aadff_conv_plan_describe) names the instantiation `dispatch`
+names, for every case here and on a sweep of the rule's thresholds.  profiles/conv_paths_coverage.md is the kernel trace of this module.
+Every case asserts
   (a) every element within the elementwise bound of its family (plain fp32 or matrix cores), no element excluded;
   (b) plain-fp32 kernels: rel_l2(got, oracle64) <= 4 x d32seq, through `margin`; matrix-core kernels report it;
   (c) every pixel written: the call goes through _abi.call into an output pre-filled with a sentinel, none survives;
