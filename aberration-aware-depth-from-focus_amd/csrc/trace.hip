@@ -218,29 +218,43 @@ __global__ __launch_bounds__(256) void trace_points_kernel(const float* __restri
 // PSF histogram: deeplens/monte_carlo.py:9-121
 // ------------------------------------------------------------------------------------
 struct SplatGeom {
-    float lo, hi, lim, den_row, den_col;   // all float64 -> fp32 once
+    float lo, hi, lim, scale, half;        // all float64 -> fp32 once
     int ks;
 };
 
+// Bin coordinates of monte_carlo.py:86-92, (Y - hi) / (lo - hi) (ks - 1) and (X - lo) / (hi - lo) (ks - 1), are, with -lo = hi,
+// -Y scale + half and X scale + half: scale = (ks - 1) / (hi - lo) pixels per mm, half = (ks - 1) / 2 (a float: the centre's coordinate)
 __host__ __device__ inline SplatGeom make_splat_geom(float pixel_size, int ks) {
     const double ps = (double)pixel_size;
     const double lo = (-ks / 2.0 + 0.5) * ps, hi = (ks / 2.0 - 0.5) * ps;
     SplatGeom g;
     g.lo = (float)lo; g.hi = (float)hi;
     g.lim = (float)(hi - 0.01 * ps);
-    g.den_row = (float)(lo - hi);
-    g.den_col = (float)(hi - lo);
+    g.scale = (float)((ks - 1) / (hi - lo));           // ks = 1: never read, the window (lim < 0) holds no hit
+    g.half = (float)((ks - 1) / 2.0);
     g.ks = ks;
     return g;
 }
 
 // hit (ox,oy) on the sensor -> 4 bilinear taps into hist[ks*ks] (LDS), weight ra
+// WEIGHTED: ra may be any weight, and the reference scales the centred hit by it as well (`points_shift *= ra`, monte_carlo.py:38)
+// before it bins it.  The traces of this file hand over 0 or 1, for which that product is the identity: only aadff_psf_splat, whose
+// caller supplies ra, asks for it.
+template <bool WEIGHTED = false>
 __device__ __forceinline__ void splat_hit(float* hist, const SplatGeom& g, float ox, float oy, float ra, float cx, float cy) {
     float X = -ox - cx, Y = -oy - cy;                 // image flip, then centre
     const bool in = (fabsf(X) < g.lim) && (fabsf(Y) < g.lim) && (ra > 0.f);
     if (!in) return;                                   // zero-weight taps at the centre bin are skipped
-    const float rowf = fdiv(Y - g.hi, g.den_row) * (float)(g.ks - 1);
-    const float colf = fdiv(X - g.lo, g.den_col) * (float)(g.ks - 1);
+    if constexpr (WEIGHTED) {
+        X *= ra; Y *= ra;
+        if (!(fabsf(X) < g.lim && fabsf(Y) < g.lim)) return;   // a weight above 1 can carry the hit past the grid, where the reference stops with an index error
+    }
+    // One fma per coordinate, and exact where it has to be: a hit on the centre (X = 0) is at `half`.  The quotient hi / (2 hi) of the
+    // reference's form came out of a bare reciprocal as 0.49999997; at ks = 3 that is column 0.99999994, and the reference's
+    // floor(f + 1), kept below, rounds 1.99999994 up to 2 - the whole weight of the ray in column 2 where the reference, dividing
+    // exactly, has it in column 1.
+    const float rowf = fmaf(-Y, g.scale, g.half);
+    const float colf = fmaf(X, g.scale, g.half);
     const float fr = floorf(rowf), fc = floorf(colf);
     const float wb = rowf - fr, wr = colf - fc;
     const int r0 = (int)fr, c0 = (int)fc;
@@ -293,7 +307,7 @@ __global__ __launch_bounds__(256) void psf_splat_kernel(const float* __restrict_
     const float cx = centre[2 * n], cy = centre[2 * n + 1];
     for (int i = threadIdx.x; i < spp; i += blockDim.x) {
         const size_t e = (size_t)i * N + n;
-        splat_hit(hist, g, o[3 * e], o[3 * e + 1], ra[e], cx, cy);
+        splat_hit<true>(hist, g, o[3 * e], o[3 * e + 1], ra[e], cx, cy);
     }
     __syncthreads();
     float part = 0.f;

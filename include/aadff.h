@@ -652,7 +652,8 @@ int aadff_sensor_uniforms(unsigned long long seed, int spp, int H, int W, float*
 /* Bilinear splat of sensor hits into ks x ks histograms + normalisation.  Replaces
  * forward_integral / assign_points_to_pixels, deeplens/monte_carlo.py:9-121 and the
  * division of deeplens/optics.py:978.  o [spp,N,3], ra [spp,N], centre [N,2];
- * psf_raw_or_null / psf [N,ks,ks]. */
+ * psf_raw_or_null / psf [N,ks,ks].  ra is a weight (0: a dead ray): as in the reference (monte_carlo.py:38) a hit inside
+ * the window is scaled by it about the centre before it is binned; one that a weight above 1 carries out of the window is dropped. */
 int aadff_psf_splat(const float* o, const float* ra, const float* centre, int spp, int N,
                     float pixel_size, int ks, float* psf_raw_or_null, float* psf,
                     aadff_stream_t stream);
