@@ -442,7 +442,8 @@ def depth_layers(depth_mm, layers):
 
 
 @torch.no_grad()
-def render_focal_stack_m1_layered(lens, img, depth_mm, focus_mm, layers=4, grid=11, ks=11, spp=GEO_SPP, fused=True, return_parts=False):
+def render_focal_stack_m1_layered(lens, img, depth_mm, focus_mm, layers=4, grid=11, ks=11, spp=GEO_SPP, fused=True, return_parts=False,
+                                  occlusion=False):
     """RGB-D aware grid rendering ("M1-layered"): the depth map is quantised into `layers`
     planes; for every focus distance and layer one PSF map is ray traced and the slice is the per-pixel
     selection  out[s] = sum_l [layer == l] * render_psf_map(img, psf_map[s, l]).
@@ -451,12 +452,16 @@ def render_focal_stack_m1_layered(lens, img, depth_mm, focus_mm, layers=4, grid=
     [B,1,H,W] (mm, < 0), focus_mm [S] (mm, < 0) -> [B,C,S,H,W].
     Round 5: three launches - refocus, ONE PSF-grid launch for all S x L (slice, layer) pairs, and (ks 11) a stack convolution that
     takes the layer-index map and writes [B,C,S,H,W] directly (`aadff_render_psf_map_stack_layered`); `fused=False` (and other ks)
-    renders the S x L candidate slices and gathers, L x the output bytes."""
+    renders the S x L candidate slices and gathers, L x the output bytes.
+    `occlusion=True` (layers <= 32, any odd ks from 3): the same refocus and PSF-grid launches on the same draws, then the layers are
+    composited front to back instead of selected per pixel (`aadff_render_psf_map_stack_occluded`, aadff/occlusion.py):
+    a blurred background no longer bleeds through a sharp foreground edge."""
     focus = [float(f) for f in np.asarray(focus_mm, dtype=np.float64).reshape(-1)]
     S, L = len(focus), int(layers)
     B, C_, H, W = img.shape
     assert tuple(lens.sensor_res) == (H, W), "lens.sensor_res must match the image"
     assert 1 <= L <= 254, "1..254 depth layers"
+    assert not occlusion or L <= 32, "occlusion=True composites at most 32 depth layers"
     dev = lens._gpu()
     x = _abi.f32c(img, dev)
     idx, centres = depth_layers(_abi.f32c(depth_mm, dev), L)
@@ -494,7 +499,12 @@ def render_focal_stack_m1_layered(lens, img, depth_mm, focus_mm, layers=4, grid=
         _abi.call("aadff_psf_points_fit_pts", _abi.ptr(pts), S * L, N, 3, _abi.ptr(tab_rgb), _abi.ptr(tab_green), lc, _abi.ptr(st_rep),
                   C.c_void_p(base), spp, layer_block, per_l, C.c_void_p(base + 4 * 2 * spp), GEO_SPP, layer_block, per_l, ks, 1, 1,
                   _abi.ptr(maps), None, _abi.ptr(flags), _abi.ptr(fit_w), _abi.ptr(fit_c), _abi.ptr(pxy), st)
-        if ks == 11 and fused:
+        if occlusion:
+            lidx = idx.reshape(B, H, W).to(torch.uint8).contiguous()
+            out = torch.empty((B, C_, S, H, W), dtype=torch.float32, device=dev)
+            _abi.call("aadff_render_psf_map_stack_occluded", _abi.ptr(x), _abi.ptr(maps), _abi.ptr(lidx), _abi.ptr(out), None, B, C_, S, L, H, W,
+                      grid, ks, 1, st)
+        elif ks == 11 and fused:
             # the L candidates of a pixel are computed from one staged band and only the pixel's own layer is written: 1 x the output
             lidx = idx.reshape(B, H, W).to(torch.uint8).contiguous()
             out = torch.empty((B, C_, S, H, W), dtype=torch.float32, device=dev)

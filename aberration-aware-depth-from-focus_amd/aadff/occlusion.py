@@ -1,0 +1,78 @@
+"""Occlusion-aware layered PSF-map rendering (csrc/conv_occl.hip): every depth layer's premultiplied image and its
+mask are blurred with that layer's grid PSFs and the layers are composited front to back with a transmittance, in one launch per
+stack.  The per-pixel layer selection of `render_focal_stack_m1_layered` lets a blurred background bleed through a sharp foreground
+edge and the reverse; this is the pixel-level form of the per-ray rule of `render_raytraced_layered`.
+
+    render_psf_map_occluded(img, maps, layer, grid, normalize=True, return_coverage=False)            -> [B,C,H,W]
+    render_psf_map_occluded_stack(img, maps, layer, L, grid, normalize=True, return_coverage=False)   -> [B,C,S,H,W]
+
+`maps` holds one PSF map per layer ([L,C,grid*ks,grid*ks]) or, for a stack, per (slice, layer) pair ([S*L,...], pair s*L + l), as
+`render_focal_stack_m1_layered(..., return_parts=True)` returns them.  `layer` [B,H,W] is uint8, or int64 as `depth_layers` returns it;
+layer 0 is the nearest and an index >= L lies on no layer (a hole: it covers nothing and shows nothing).  With `normalize` the
+composite V is divided by the accumulated coverage A where A > 0 (0 elsewhere); `return_coverage` adds A as a second result.  The rule,
+tap order included, is the arithmetic contract of `aadff_render_psf_map_stack_occluded` in include/aadff.h.
+Forward only: tensors that require grad are refused.  The functions call the C entry directly; there is no torch custom op for it: the
+set of `torch.ops.aadff` ops is a recorded one (tests/golden/ops_schemas.json).
+"""
+import torch
+
+from . import _abi
+
+MAX_LAYERS = 32                     # AADFF_RENDER_MAX_LAYERS: the presence mask of a tile is one 32-bit word
+
+
+def _layer_u8(layer, B, H, W, L):
+    """The layer map as uint8 [B,H,W]; int64 values outside 0 .. 255 are refused (they would wrap into a layer)."""
+    assert tuple(layer.shape) == (B, H, W), "layer should be [B, H, W]"
+    assert layer.dtype in (torch.uint8, torch.int64), "layer should be uint8 or int64"
+    if layer.dtype == torch.int64 and layer.numel():
+        lo, hi = int(layer.min()), int(layer.max())
+        assert 0 <= lo and hi <= 255, f"layer values should be in 0..255 (an index >= L = {L} is a hole), got {lo}..{hi}"
+        layer = layer.to(torch.uint8)
+    return layer
+
+
+def render_psf_map_occluded_stack(img, maps, layer, L, grid, normalize=True, return_coverage=False):
+    """img [B,C,H,W], maps [S*L,C,grid*ks,grid*ks], layer [B,H,W] -> [B,C,S,H,W] (and the coverage A [B,C,S,H,W]): slice s is the
+    front-to-back composite of the L layers blurred with maps s*L .. s*L + L-1; equal to the slices rendered one by one bit for bit,
+    with the image and layer tiles staged once for all S slices."""
+    assert len(img.shape) == 4, "Input image should be [B, C, H, W]"
+    assert len(maps.shape) == 4, "PSF maps should be [S*L, C, grid*ks, grid*ks]"
+    L, grid = int(L), int(grid)
+    assert 1 <= L <= MAX_LAYERS, f"L should be in 1..{MAX_LAYERS}"
+    SL, Cpsf, Hpsf, Wpsf = maps.shape
+    assert SL % L == 0, "PSF maps should hold L maps per slice"
+    assert grid >= 1 and Hpsf % grid == 0 and Wpsf % grid == 0 and Hpsf == Wpsf, "PSF map size should be divisible by grid"
+    ks = Hpsf // grid
+    assert ks % 2 == 1, "PSF kernel size should be odd"
+    assert 3 <= ks <= _abi.MAX_KS, f"PSF kernel size should be in 3..{_abi.MAX_KS}"
+    B, C_, H, W = img.shape
+    assert C_ == Cpsf, "PSF map should have the same channel as image"
+    S = SL // L
+    lay = _layer_u8(layer, B, H, W, L)
+    if (img.requires_grad or maps.requires_grad) and torch.is_grad_enabled():
+        raise RuntimeError("render_psf_map_occluded_stack: forward-only HIP op, call it under torch.no_grad() or detach the input")
+    if img.numel() == 0 or S == 0:
+        out = torch.empty((B, C_, S, H, W), dtype=torch.float32, device=img.device)
+        return (out, torch.empty_like(out)) if return_coverage else out
+    _abi.require_gpu()
+    dev = img.device if img.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    x, p, li = _abi.f32c(img, dev), _abi.f32c(maps, dev), lay.to(dev).contiguous()
+    out = x.new_empty((B, C_, S, H, W))
+    cov = x.new_empty((B, C_, S, H, W)) if return_coverage else None
+    with _abi.on_device(dev):
+        _abi.call("aadff_render_psf_map_stack_occluded", _abi.ptr(x), _abi.ptr(p), _abi.ptr(li), _abi.ptr(out), _abi.ptr(cov), B, C_, S, L, H, W,
+                  grid, ks, 1 if normalize else 0, _abi.stream_ptr(dev))
+    if return_coverage:
+        return out.to(img.device), cov.to(img.device)
+    return out.to(img.device)
+
+
+def render_psf_map_occluded(img, maps, layer, grid, normalize=True, return_coverage=False):
+    """img [B,C,H,W], maps [L,C,grid*ks,grid*ks] (one map per layer), layer [B,H,W] -> [B,C,H,W]: the occlusion-aware sibling of the
+    per-pixel layer selection."""
+    assert len(maps.shape) == 4, "PSF maps should be [L, C, grid*ks, grid*ks]"
+    res = render_psf_map_occluded_stack(img, maps, layer, maps.shape[0], grid, normalize, return_coverage)
+    if return_coverage:
+        return res[0][:, :, 0], res[1][:, :, 0]
+    return res[:, :, 0]

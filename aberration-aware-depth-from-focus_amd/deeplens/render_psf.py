@@ -14,6 +14,7 @@ import torch
 from aadff import _abi
 from aadff import ops as _ops      # noqa: F401  (registers torch.ops.aadff.*)
 from aadff.blend import render_psf_map_blend, render_psf_map_blend_stack      # noqa: F401  (the seam-free twins of render_psf_map[_stack])
+from aadff.occlusion import render_psf_map_occluded, render_psf_map_occluded_stack      # noqa: F401  (the occlusion-aware layered composite)
 
 
 def _prep(t, what):

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""One RGB-D scene through the lens twice: ray traced with occlusion, and by the layered PSF-grid approximation.
+"""One RGB-D scene through the lens three times: ray traced with occlusion, by the layered PSF-grid approximation with a per-pixel
+layer selection, and by the same PSF grids composited front to back (occlusion-aware).
 
     python examples/raytraced_rgbd_vs_layered_psf.py [--lens rf50mm] [--size 256 256] [--layers 8] [--spp 64] [--band 8] [--out .]
 
@@ -12,8 +13,12 @@ the depth map with the same `aadff.focal_stack.depth_layers`:
 2. `render_focal_stack_m1_layered(lens, img, depth, focus, layers)`: per layer one 11 x 11 grid of PSFs, each pixel takes the
    render of its own layer.  No occlusion: next to the edge, a pixel's PSF gathers texels of the other surface as if they lay at its
    own depth.
-The lens is focused once on the disc and once on the background behind it.  Printed: mean |difference| (green) inside a band of
-`--band` pixels around the disc's edge and outside it, per focus.  The ray-traced renders are saved as PNG.
+3. `render_focal_stack_m1_layered(..., occlusion=True)`: the same refocus and PSF-grid launches; per layer the premultiplied image and
+   the mask are blurred with the layer's PSFs and the layers are composited front to back with a transmittance
+   (aadff.occlusion) - the pixel-level form of route 1's per-ray rule.
+The lens is focused once on the disc and once on the background behind it.  Printed: mean |difference| (green) to the ray-traced picture
+inside a band of `--band` pixels around the disc's edge and outside it, per focus, for both PSF routes.  The ray-traced renders are
+saved as PNG.
 """
 import argparse
 import os
@@ -47,7 +52,10 @@ depth_np, disc = synth_disc_depth_mm(H, W)
 depth = torch.from_numpy(depth_np)[None, None].to(DEV)
 focus = [float(depth_np[disc].mean()), float(depth_np[H // 2, :][~disc[H // 2, :]].mean())]          # the disc, the background beside it
 
+torch.manual_seed(0)
 by_psf = render_focal_stack_m1_layered(lens, img, depth, focus, layers=a.layers)                      # [1,3,2,H,W]
+torch.manual_seed(0)                                                                                  # the same draws: the same PSF grids
+by_occl = render_focal_stack_m1_layered(lens, img, depth, focus, layers=a.layers, occlusion=True)
 traced = []
 for k, fd in enumerate(focus):
     lens.refocus(fd)
@@ -59,11 +67,12 @@ traced = torch.stack(traced, dim=2)
 yy, xx = np.mgrid[0:H, 0:W]
 rad = np.sqrt((yy - (H - 1) / 2) ** 2 + (xx - (W - 1) / 2) ** 2)
 edge = torch.from_numpy(np.abs(rad - rad[disc].max()) <= a.band).to(DEV)
-diff = (traced - by_psf).abs()[0, 1]                                                                  # green, [2,H,W]
+diffs = {"select": (traced - by_psf).abs()[0, 1], "occlusion-aware": (traced - by_occl).abs()[0, 1]}          # green, [2,H,W]
 print(f"{a.lens} at {H} x {W}, {a.layers} layers at {[round(float(z)) for z in zs[0]]} mm, {a.spp} rays per pixel and channel")
 print(f"mean |ray-traced - layered PSF grid| (green, image range 0..1), band = {a.band} px around the disc's edge")
 for k, (fd, what) in enumerate(zip(focus, ("disc", "background"))):
-    print(f"  focus {fd:8.1f} mm ({what:10s})  inside the band {float(diff[k][edge].mean()):.4f}   outside {float(diff[k][~edge].mean()):.4f}")
+    for route, diff in diffs.items():
+        print(f"  focus {fd:8.1f} mm ({what:10s})  {route:15s}  inside the band {float(diff[k][edge].mean()):.4f}   outside {float(diff[k][~edge].mean()):.4f}")
     path = os.path.join(a.out, f"render_raytraced_rgbd_{what}.png")
     save_image(traced[0, :, k].clamp(0, 1), path)
     print("  wrote", path)

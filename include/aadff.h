@@ -159,6 +159,33 @@ int aadff_render_psf_map_blend_stack(const float* img, const float* psf_maps, fl
                                      const float* node_y, const float* node_x,
                                      int B, int C, int S, int H, int W, int grid, int ks, aadff_stream_t stream);
 
+/* Occlusion-aware layered PSF-map rendering (no reference counterpart; the layered defocus composite, the pixel-level form of the
+ * per-ray rule of aadff_render_raytraced_layered): every layer's premultiplied image and its mask are blurred with that layer's PSF and
+ * the layers are composited front to back with a transmittance, in one launch per stack (csrc/conv_occl.hip).
+ * img [B,C,H,W]; psf_maps [S*L,C,g*ks,g*ks], pair p = s*L + l, tile (i,j) as aadff_render_psf_map reads it; layer [B,H,W] uint8, layer 0
+ * the nearest, a texel whose index is >= L lies on no layer (a hole); out [B,C,S,H,W]; coverage_or_null [B,C,S,H,W] or NULL.
+ * Arithmetic contract, per output pixel (b,c,s,y,x) of patch (i,j) (patch bounds int(i/grid*n), as aadff_render_psf_map):
+ *   1. w_l(u,v) = psf[ks-1-u][ks-1-v] of tile (i,j) of map s*L + l, channel c (the flipped tile).
+ *   2. The image and the layer map are reflect-padded by ks/2 with the same index reflection; tap t = (u,v) reads texel
+ *      (reflect(y - ks/2 + u), reflect(x - ks/2 + v)).
+ *   3. m_l(t) = (layer[b,t] == l).
+ *   4. a_l = sum_t w_l(t) (m_l(t) ? 1 : 0): the coverage, one fp32 fma chain a = fma(w, m, a) from 0 over the taps in row-major order
+ *      (u = 0 .. ks-1, inside it v = 0 .. ks-1).
+ *   5. q_l = sum_t w_l(t) (m_l(t) ? img[b,c,t] : 0): the radiance, a second chain of the same form in the same tap order.  The mask is
+ *      a SELECT, not a product: a NaN or Inf on a texel of another layer or of a hole does not reach the output.
+ *   6. T = 1, V = 0, A = 0; for l = 0 .. L-1 in this order: V = fma(T, q_l, V); A = fma(T, a_l, A); T = T * max(1 - a_l, 0)
+ *      (each operation rounded once, fp32).
+ *   7. normalize != 0: out = V / A (IEEE division) where A > 0, else 0; normalize == 0: out = V.  coverage = A.
+ * Consequences that hold exactly: a layer none of whose window texels carries index l has a_l = q_l = 0 and leaves V, A, T unchanged
+ * (the kernel skips the layers absent from the staged tile: no bit changes); if every window texel is on layer k, V = q_k and A = a_k;
+ * scaling the image by a power of two scales V by the same factor bit for bit.  No atomics, every output written once, a repeat equals
+ * itself bit for bit, a stack equals its slices and a batch its images.  Forward only.  All arguments are validated before any HIP
+ * call: NULL pointers (coverage may be NULL), even ks, ks outside 3 .. AADFF_MAX_KS, L outside 1 .. AADFF_RENDER_MAX_LAYERS (defined
+ * below, 32), grid outside 1 .. AADFF_MAX_GRID or above min(H, W), H or W <= ks/2 and sizes too large for one launch give AADFF_EINVAL. */
+int aadff_render_psf_map_stack_occluded(const float* img, const float* psf_maps, const unsigned char* layer, float* out,
+                                        float* coverage_or_null, int B, int C, int S, int L, int H, int W, int grid, int ks,
+                                        int normalize, aadff_stream_t stream);
+
 /* Measurement aid (no reference counterpart): arm the NEXT aadff_render_psf_map_stack (slice-batched kernel: ks 11, S >= 3)
  * or aadff_psf_points / aadff_psf_points_staged call made by this host thread so that its kernel is launched with the two
  * HIP events (hipEvent_t, timing enabled) attached to the dispatch (hipExtLaunchKernelGGL): hipEventElapsedTime then gives
