@@ -97,6 +97,7 @@ PROTOTYPES = {
     "aadff_render_psf_map_blend_stack": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "aadff_render_psf_map_blend_stack_bwd": [_P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "aadff_render_psf_map_stack_occluded": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "aadff_render_psf_map_stack_occluded_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "aadff_time_next_launch": [_P, _P],
     "aadff_render_psf": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "aadff_conv_plan_describe": [C.c_char_p, _I, _I, _I, _I, _I, _I, _I, _I, _L, _L, C.c_char_p, _I, C.POINTER(C.c_longlong)],
@@ -186,6 +187,7 @@ OTHER_SYMBOLS = ["aadff_abi_version", "aadff_last_error", "aadff_device_info"]
 # name -> argtypes of the entries that return a byte count (size_t; 0 = rejected, aadff_last_error says why)
 SIZE_PROTOTYPES = {
     "aadff_render_psf_map_blend_stack_bwd_workspace": [_I, _I, _I, _I, _I, _I, _I],
+    "aadff_render_psf_map_stack_occluded_bwd_workspace": [_I, _I, _I, _I, _I, _I, _I, _I, _I],
 }
 
 _lib = None

@@ -26,7 +26,14 @@ the four grid PSFs around it) with gradients to the image and the PSF maps from 
 the forward-only kernel, bit for bit, the backward calls aadff_render_psf_map_blend_stack_bwd through the C ABI (no torch custom op),
 computes only the gradients autograd asks for and keeps nothing but the two inputs in between.  `grid` and `nodes` get no gradient.
 
-Not covered: gradients through the ray tracer and the M1-layered stack; gradients to the nodes of the blended render.
+`render_psf_map_occluded` / `render_psf_map_occluded_stack` are the occlusion-aware layered renders of aadff/occlusion.py (every layer's
+premultiplied image and mask blurred with that layer's PSFs, composited front to back) with gradients to the image and the PSF maps from
+csrc/conv_occl_bwd.hip: the forward is the forward-only kernel, bit for bit; the backward calls
+aadff_render_psf_map_stack_occluded_bwd through the C ABI, recomputes the per-layer sums, computes only the gradients autograd asks for
+and keeps nothing but the inputs in between.  With `return_coverage` both results are differentiable.  The layer map gets no gradient.
+
+Not covered: gradients through the ray tracer and the M1-layered stack; gradients to the nodes of the blended render and to a depth map
+behind the layer map of the occluded render.
 """
 import ctypes as C
 import importlib
@@ -208,6 +215,92 @@ def render_psf_map_blend(img, psf_map, grid, nodes="psf_map"):
     """aadff.blend.render_psf_map_blend with gradients: img [B,C,H,W], psf_map [C,grid*ks,grid*ks] -> [B,C,H,W]."""
     assert len(psf_map.shape) == 3, "PSF map should be [C, grid*ks, grid*ks]"
     return render_psf_map_blend_stack(img, psf_map[None], grid, nodes)[:, :, 0]
+
+
+# ---------------------------------------------------------------- occlusion-aware layered render (aadff/occlusion.py, csrc/conv_occl_bwd.hip)
+OCCL_WORKSPACE_CAP = 1 << 30          # bytes of backward workspace above which a stack is taken in several passes
+
+
+class _OcclStack(torch.autograd.Function):
+    """x [B,C,H,W], p [S L,C,g ks,g ks] float32 and lay [B,H,W] uint8, contiguous on the GPU -> (out, coverage) [B,C,S,H,W]."""
+
+    @staticmethod
+    def forward(ctx, x, p, lay, L, grid, normalize):
+        B, C_, H, W = x.shape
+        S, ks = p.shape[0] // L, p.shape[-1] // grid
+        out, cov = x.new_empty((B, C_, S, H, W)), x.new_empty((B, C_, S, H, W))
+        with _abi.on_device(x.device):
+            _abi.call("aadff_render_psf_map_stack_occluded", _abi.ptr(x), _abi.ptr(p), _abi.ptr(lay), _abi.ptr(out), _abi.ptr(cov), B, C_, S, L, H, W,
+                      grid, ks, normalize, _abi.stream_ptr(x.device))
+        ctx.save_for_backward(x, p, lay)
+        ctx.set_materialize_grads(False)         # an unused result's gradient arrives as None and goes to the entry as NULL
+        ctx.args = (L, grid, normalize)
+        return out, cov
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, h):
+        x, p, lay = ctx.saved_tensors
+        L, grid, normalize = ctx.args
+        B, C_, H, W = x.shape
+        S, ks = p.shape[0] // L, p.shape[-1] // grid
+        want_img, want_maps = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        g = None if g is None else _abi.f32c(g, x.device)
+        h = None if h is None else _abi.f32c(h, x.device)
+        if g is None and h is None:
+            return (torch.zeros_like(x) if want_img else None), (torch.zeros_like(p) if want_maps else None), None, None, None, None
+        d_img = torch.empty_like(x) if want_img else None
+        d_maps = torch.empty_like(p) if want_maps else None
+        query = _abi.load_library().aadff_render_psf_map_stack_occluded_bwd_workspace
+        nbytes = query(B, C_, S, L, H, W, grid, ks, 1 if want_maps else 0)
+        if nbytes > OCCL_WORKSPACE_CAP:          # fewer slices per pass, never below one: the gradients are bit-equal for every size
+            one = query(B, C_, 1, L, H, W, grid, ks, 1 if want_maps else 0)
+            nbytes = max(one, OCCL_WORKSPACE_CAP // one * one)
+        ws = _abi.workspace(x, nbytes)
+        with _abi.on_device(x.device):
+            _abi.call("aadff_render_psf_map_stack_occluded_bwd", _abi.ptr(x), _abi.ptr(p), _abi.ptr(lay), _abi.ptr(g), _abi.ptr(h), _abi.ptr(d_img),
+                      _abi.ptr(d_maps), _abi.ptr(ws), C.c_size_t(nbytes), B, C_, S, L, H, W, grid, ks, normalize, _abi.stream_ptr(x.device))
+        return d_img, d_maps, None, None, None, None
+
+
+def render_psf_map_occluded_stack(img, maps, layer, L, grid, normalize=True, return_coverage=False):
+    """aadff.occlusion.render_psf_map_occluded_stack with gradients: img [B,C,H,W], maps [S*L,C,grid*ks,grid*ks], layer [B,H,W] (uint8 or
+    int64, an index >= L a hole) -> [B,C,S,H,W], and the coverage with `return_coverage`; both are differentiable.  d_img is the sum over
+    the slices, d_maps the sum over the batch; the layer map gets no gradient.  Under torch.no_grad(), or when neither input requires
+    grad, this IS the forward-only function.  Double backward raises."""
+    from . import occlusion
+    if not _wants_grad(img, maps):
+        return occlusion.render_psf_map_occluded_stack(img, maps, layer, L, grid, normalize, return_coverage)
+    assert len(img.shape) == 4, "Input image should be [B, C, H, W]"
+    assert len(maps.shape) == 4, "PSF maps should be [S*L, C, grid*ks, grid*ks]"
+    L, grid = int(L), int(grid)
+    assert 1 <= L <= occlusion.MAX_LAYERS, f"L should be in 1..{occlusion.MAX_LAYERS}"
+    SL, Cpsf, Hpsf, Wpsf = maps.shape
+    assert SL % L == 0, "PSF maps should hold L maps per slice"
+    assert grid >= 1 and Hpsf % grid == 0 and Wpsf % grid == 0 and Hpsf == Wpsf, "PSF map size should be divisible by grid"
+    ks = Hpsf // grid
+    assert ks % 2 == 1, "PSF kernel size should be odd"
+    assert 3 <= ks <= _abi.MAX_KS, f"PSF kernel size should be in 3..{_abi.MAX_KS}"
+    B, C_, H, W = img.shape
+    assert C_ == Cpsf, "PSF map should have the same channel as image"
+    S = SL // L
+    lay = occlusion._layer_u8(layer, B, H, W, L)
+    if img.numel() == 0 or S == 0:
+        out = _empty(img, maps, (B, C_, S, H, W))
+        return (out, out * 1) if return_coverage else out
+    dev = _dev(img)
+    out, cov = _OcclStack.apply(_abi.f32c(img, dev), _abi.f32c(maps, dev), lay.to(dev).contiguous(), L, grid, 1 if normalize else 0)
+    return (out.to(img.device), cov.to(img.device)) if return_coverage else out.to(img.device)
+
+
+def render_psf_map_occluded(img, maps, layer, grid, normalize=True, return_coverage=False):
+    """aadff.occlusion.render_psf_map_occluded with gradients: img [B,C,H,W], maps [L,C,grid*ks,grid*ks] (one map per layer),
+    layer [B,H,W] -> [B,C,H,W] (and the coverage)."""
+    assert len(maps.shape) == 4, "PSF maps should be [L, C, grid*ks, grid*ks]"
+    res = render_psf_map_occluded_stack(img, maps, layer, maps.shape[0], grid, normalize, return_coverage)
+    if return_coverage:
+        return res[0][:, :, 0], res[1][:, :, 0]
+    return res[:, :, 0]
 
 
 # ---------------------------------------------------------------- PSF-network renderers (deeplens/psfnet.py:393-450)

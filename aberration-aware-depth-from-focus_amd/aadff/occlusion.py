@@ -11,7 +11,8 @@ edge and the reverse; this is the pixel-level form of the per-ray rule of `rende
 layer 0 is the nearest and an index >= L lies on no layer (a hole: it covers nothing and shows nothing).  With `normalize` the
 composite V is divided by the accumulated coverage A where A > 0 (0 elsewhere); `return_coverage` adds A as a second result.  The rule,
 tap order included, is the arithmetic contract of `aadff_render_psf_map_stack_occluded` in include/aadff.h.
-Forward only: tensors that require grad are refused.  The functions call the C entry directly; there is no torch custom op for it: the
+Forward only: tensors that require grad are refused (the differentiable twins of the same names are in aadff.diffrender, DESIGN.md
+4.21).  The functions call the C entry directly; there is no torch custom op for it: the
 set of `torch.ops.aadff` ops is a recorded one (tests/golden/ops_schemas.json).
 """
 import torch

@@ -179,12 +179,42 @@ int aadff_render_psf_map_blend_stack(const float* img, const float* psf_maps, fl
  * Consequences that hold exactly: a layer none of whose window texels carries index l has a_l = q_l = 0 and leaves V, A, T unchanged
  * (the kernel skips the layers absent from the staged tile: no bit changes); if every window texel is on layer k, V = q_k and A = a_k;
  * scaling the image by a power of two scales V by the same factor bit for bit.  No atomics, every output written once, a repeat equals
- * itself bit for bit, a stack equals its slices and a batch its images.  Forward only.  All arguments are validated before any HIP
+ * itself bit for bit, a stack equals its slices and a batch its images.  Gradients: the _bwd entry below.  All arguments are validated before any HIP
  * call: NULL pointers (coverage may be NULL), even ks, ks outside 3 .. AADFF_MAX_KS, L outside 1 .. AADFF_RENDER_MAX_LAYERS (defined
  * below, 32), grid outside 1 .. AADFF_MAX_GRID or above min(H, W), H or W <= ks/2 and sizes too large for one launch give AADFF_EINVAL. */
 int aadff_render_psf_map_stack_occluded(const float* img, const float* psf_maps, const unsigned char* layer, float* out,
                                         float* coverage_or_null, int B, int C, int S, int L, int H, int W, int grid, int ks,
                                         int normalize, aadff_stream_t stream);
+
+/* Gradients of aadff_render_psf_map_stack_occluded to the image and the PSF maps (csrc/conv_occl_bwd.hip).  The layer
+ * map is integral and gets none.  d_out_or_null = g and d_cov_or_null = h [B,C,S,H,W] are the upstream gradients to `out` and to the
+ * coverage; either may be NULL and then counts as 0 (both NULL: AADFF_EINVAL).  d_img_or_null [B,C,H,W], d_maps_or_null
+ * [S*L,C,g*ks,g*ks]: only the ones given are computed (both NULL: AADFF_EINVAL).  With q_l, a_l, T_l, V, A, out of the forward's
+ * contract (recomputed with the forward's chains, bit for bit) and f_l = max(1 - a_l, 0), per element (b,c,s,pi):
+ *   1. normalize and A > 0: gV = g / A, gA = fma(-gV, out, h) (= h - g out / A); normalize and A = 0: gV = 0, gA = h;
+ *      normalize == 0: gV = g, gA = h.
+ *   2. Back to front: R_L = 0, G_l = fma(gV, q_l, gA * a_l), R_l = fma(f_l, R_{l+1}, G_l); then front to back with T_0 = 1:
+ *      alpha_l = dL/dq_l = gV * T_l,   beta_l = dL/da_l = gA * T_l - [1 - a_l > 0] T_l R_{l+1}  (fma(-T_l, R_{l+1}, gA * T_l)),
+ *      T_{l+1} = T_l * f_l.  The indicator is the derivative of the clamp, 0 at equality.  T_l R_{l+1} is never formed as a quotient.
+ *   3. With refl the forward's reflect padding, p = ks/2, and the PSF belonging to the SOURCE pixel's patch (as
+ *      aadff_render_psf_map_stack_bwd):
+ *        d_img[b,c,t] = sum_s sum_{pi, tap : refl(pi + tap - p) = t} alpha_{layer[b,t]}(b,c,s,pi) w^{s,layer[b,t]}_{patch(pi)}(tap)
+ *      a SELECT by the texel's layer, not a sum over layers; a hole texel gets exactly 0; mirror folds as the patch route's d_img;
+ *        d_maps[s L + l, c, i ks + a, j ks + e] = sum_b sum_{pi in patch(i,j)} alpha_l(pi) (m_l(t) ? img[b,c,t] : 0) + beta_l(pi) (m_l(t) ? 1 : 0),
+ *      t = refl(pi + p - (a,e)): the image enters through a select, so a NaN on a hole or on another layer's texel reaches no
+ *      gradient; the maps of a layer that occurs nowhere in the batch get exact zeros.
+ * Plain fp32 fma, every sum in a fixed order, no float atomics, every output element written exactly once, bit-reproducible.  The
+ * d_img sum over the slices runs in ascending s, each slice's whole contribution added as one value to a running sum that starts at 0.
+ * Workspace: DEVICE memory of at least aadff_render_psf_map_stack_occluded_bwd_workspace(B, C, 1, L, H, W, grid, ks, d_maps != NULL)
+ * bytes: alpha and beta per (b,c,s,l,pixel) plus, for d_maps, one partial per 32 x 32 tile.  The entry processes as many slices per
+ * pass as fit; the query for the call's own S is the size at which one pass suffices; results are bit-equal for every admissible
+ * size.  The workspace need not be initialised.  The argument domain and the messages are the forward's; everything is validated
+ * before any HIP call.  The query returns 0 for a shape the call rejects. */
+int aadff_render_psf_map_stack_occluded_bwd(const float* img, const float* psf_maps, const unsigned char* layer,
+                                            const float* d_out_or_null, const float* d_cov_or_null, float* d_img_or_null,
+                                            float* d_maps_or_null, void* workspace, size_t workspace_bytes, int B, int C, int S, int L,
+                                            int H, int W, int grid, int ks, int normalize, aadff_stream_t stream);
+size_t aadff_render_psf_map_stack_occluded_bwd_workspace(int B, int C, int S, int L, int H, int W, int grid, int ks, int need_maps);
 
 /* Measurement aid (no reference counterpart): arm the NEXT aadff_render_psf_map_stack (slice-batched kernel: ks 11, S >= 3)
  * or aadff_psf_points / aadff_psf_points_staged call made by this host thread so that its kernel is launched with the two
