@@ -98,6 +98,7 @@ PROTOTYPES = {
     "aadff_render_psf_map_blend_stack_bwd": [_P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "aadff_render_psf_map_stack_occluded": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "aadff_render_psf_map_stack_occluded_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "aadff_render_psf_map_stack_soft_occluded": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "aadff_time_next_launch": [_P, _P],
     "aadff_render_psf": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "aadff_conv_plan_describe": [C.c_char_p, _I, _I, _I, _I, _I, _I, _I, _I, _L, _L, C.c_char_p, _I, C.POINTER(C.c_longlong)],

@@ -455,7 +455,13 @@ def render_focal_stack_m1_layered(lens, img, depth_mm, focus_mm, layers=4, grid=
     renders the S x L candidate slices and gathers, L x the output bytes.
     `occlusion=True` (layers <= 32, any odd ks from 3): the same refocus and PSF-grid launches on the same draws, then the layers are
     composited front to back instead of selected per pixel (`aadff_render_psf_map_stack_occluded`, aadff/occlusion.py):
-    a blurred background no longer bleeds through a sharp foreground edge."""
+    a blurred background no longer bleeds through a sharp foreground edge.
+    `occlusion="soft"` (layers <= 32): the layers are NODES in depth (`aadff.occlusion.depth_nodes`, the field points at the node
+    depths), the same launches on the same draws, and the last step is `aadff_render_psf_map_stack_soft_occluded`:
+    every texel takes the PSF interpolated between the two nodes around its depth.  `return_parts` then returns the float layer
+    coordinate [B,H,W] in place of the index map."""
+    assert occlusion in (False, True, "soft"), "occlusion should be False, True or 'soft'"
+    soft = occlusion == "soft"
     focus = [float(f) for f in np.asarray(focus_mm, dtype=np.float64).reshape(-1)]
     S, L = len(focus), int(layers)
     B, C_, H, W = img.shape
@@ -464,7 +470,11 @@ def render_focal_stack_m1_layered(lens, img, depth_mm, focus_mm, layers=4, grid=
     assert not occlusion or L <= 32, "occlusion=True composites at most 32 depth layers"
     dev = lens._gpu()
     x = _abi.f32c(img, dev)
-    idx, centres = depth_layers(_abi.f32c(depth_mm, dev), L)
+    if soft:
+        from .occlusion import depth_nodes
+        pos, centres = depth_nodes(_abi.f32c(depth_mm, dev), L)
+    else:
+        idx, centres = depth_layers(_abi.f32c(depth_mm, dev), L)
     N, nb = grid * grid, C.sizeof(_abi.LensState)
     per, o_main, o_chief, per_l = stack_uniform_layout(spp)              # per-layer block = per - 2*GEO_SPP
     layer_block = per - o_main
@@ -499,7 +509,12 @@ def render_focal_stack_m1_layered(lens, img, depth_mm, focus_mm, layers=4, grid=
         _abi.call("aadff_psf_points_fit_pts", _abi.ptr(pts), S * L, N, 3, _abi.ptr(tab_rgb), _abi.ptr(tab_green), lc, _abi.ptr(st_rep),
                   C.c_void_p(base), spp, layer_block, per_l, C.c_void_p(base + 4 * 2 * spp), GEO_SPP, layer_block, per_l, ks, 1, 1,
                   _abi.ptr(maps), None, _abi.ptr(flags), _abi.ptr(fit_w), _abi.ptr(fit_c), _abi.ptr(pxy), st)
-        if occlusion:
+        if soft:
+            pos = pos.reshape(B, H, W).contiguous()
+            out = torch.empty((B, C_, S, H, W), dtype=torch.float32, device=dev)
+            _abi.call("aadff_render_psf_map_stack_soft_occluded", _abi.ptr(x), _abi.ptr(maps), _abi.ptr(pos), _abi.ptr(out), None, B, C_, S, L,
+                      H, W, grid, ks, 1, st)
+        elif occlusion:
             lidx = idx.reshape(B, H, W).to(torch.uint8).contiguous()
             out = torch.empty((B, C_, S, H, W), dtype=torch.float32, device=dev)
             _abi.call("aadff_render_psf_map_stack_occluded", _abi.ptr(x), _abi.ptr(maps), _abi.ptr(lidx), _abi.ptr(out), None, B, C_, S, L, H, W,
@@ -517,6 +532,8 @@ def render_focal_stack_m1_layered(lens, img, depth_mm, focus_mm, layers=4, grid=
     lens._state_device().copy_(states[(S - 1) * nb:S * nb])
     lens._state_stale = True
     lens._m1l_flags = flags                                               # raise_psf_flags(int(flags.item())) is the caller's (synchronising) check
+    if return_parts and soft:                                             # (stack, PSF maps [S*L,3,g*ks,g*ks], layer coordinate [B,H,W] float32)
+        return out, maps, pos
     if return_parts:                                                      # (stack, PSF maps [S*L,3,g*ks,g*ks], layer index [B,H,W] uint8)
         return out, maps, idx.reshape(B, H, W).to(torch.uint8).contiguous()
     return out

@@ -1123,14 +1123,20 @@ class Lensgroup(DeepObj):
         return render_psf_map_blend(img, self.psf_map(depth=depth, grid=grid, ks=ks, spp=spp), grid)
 
     @torch.no_grad()
-    def render_occluded(self, img, depth_mm, layers=8, grid=11, ks=11, spp=GEO_SPP):
+    def render_occluded(self, img, depth_mm, layers=8, grid=11, ks=11, spp=GEO_SPP, soft=False):
         """img [B,3,H,W] and depth_mm [B,1,H,W] (mm, < 0) at this lens' sensor resolution and current focus, rendered with occlusion:
         `aadff.focal_stack.depth_layers`, one `psf_map` per layer centre (nearest first), and the front-to-back composite
-        `aadff.occlusion.render_psf_map_occluded`."""
+        `aadff.occlusion.render_psf_map_occluded`.  `soft=True`: the layers are nodes in depth
+        (`aadff.occlusion.depth_nodes`), one `psf_map` per node, and every texel takes the PSF interpolated between the two nodes around
+        its depth (`aadff.occlusion.render_psf_map_soft_occluded`)."""
         from aadff.focal_stack import depth_layers
-        from aadff.occlusion import render_psf_map_occluded
+        from aadff.occlusion import depth_nodes, render_psf_map_occluded, render_psf_map_soft_occluded
         assert len(img.shape) == 4 and tuple(img.shape[-2:]) == tuple(self.sensor_res), "Input image should be [B, C, H, W] at the sensor resolution"
         B, _, H, W = img.shape
+        if soft:
+            pos, nodes = depth_nodes(depth_mm.to(self._gpu(), torch.float32), int(layers))
+            maps = torch.stack([self.psf_map(depth=float(z), grid=grid, ks=ks, spp=spp) for z in nodes.tolist()])
+            return render_psf_map_soft_occluded(img, maps, pos.reshape(B, H, W), grid)
         idx, centres = depth_layers(depth_mm.to(self._gpu(), torch.float32), int(layers))
         maps = torch.stack([self.psf_map(depth=float(z), grid=grid, ks=ks, spp=spp) for z in centres.tolist()])
         return render_psf_map_occluded(img, maps, idx.reshape(B, H, W), grid)

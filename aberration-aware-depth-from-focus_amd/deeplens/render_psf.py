@@ -15,6 +15,7 @@ from aadff import _abi
 from aadff import ops as _ops      # noqa: F401  (registers torch.ops.aadff.*)
 from aadff.blend import render_psf_map_blend, render_psf_map_blend_stack      # noqa: F401  (the seam-free twins of render_psf_map[_stack])
 from aadff.occlusion import render_psf_map_occluded, render_psf_map_occluded_stack      # noqa: F401  (the occlusion-aware layered composite)
+from aadff.occlusion import render_psf_map_soft_occluded, render_psf_map_soft_occluded_stack      # noqa: F401  (its soft-depth-layer form)
 
 
 def _prep(t, what):

@@ -216,6 +216,35 @@ int aadff_render_psf_map_stack_occluded_bwd(const float* img, const float* psf_m
                                             int H, int W, int grid, int ks, int normalize, aadff_stream_t stream);
 size_t aadff_render_psf_map_stack_occluded_bwd_workspace(int B, int C, int S, int L, int H, int W, int grid, int ks, int need_maps);
 
+/* Soft depth layers for the occlusion-aware layered render (csrc/conv_occl_soft.hip): the L maps of a slice are NODES
+ * in depth, every texel carries a continuous layer coordinate and is blurred with the PSF interpolated linearly between the two nodes
+ * around it; the slabs between nodes are composited front to back by the rule of aadff_render_psf_map_stack_occluded.
+ * img [B,C,H,W]; psf_maps [S*L,C,g*ks,g*ks], node l of slice s is map s*L + l, node 0 the nearest, tiles as aadff_render_psf_map reads
+ * them; pos [B,H,W] float32, the texel's layer coordinate; 1 <= L <= AADFF_RENDER_MAX_LAYERS; out, coverage_or_null [B,C,S,H,W].
+ * Arithmetic contract.  Per texel t:
+ *   1. !(pos >= 0) (NaN included): a hole, it covers nothing and shows nothing.  Otherwise p = min(pos, L-1), slab k = min((int)p, L-1),
+ *      f = p - k: exact in float32, in [0,1).  Slab L-1 has node L-1 alone and is reached only at p = L-1, with f = 0.
+ *   2. m0 = fl(1 - f), m1 = f, x0 = fl(m0 * img[b,c,t]), x1 = fl(m1 * img[b,c,t]).
+ * Per output pixel (b,c,s,y,x) of patch (i,j), with w_k the flipped tile (i,j) of map s*L + k, channel c, and img and pos reflect-padded
+ * by ks/2 alike (steps 1, 2 of the contract above):
+ *   3. Per slab k four fp32 fma chains from 0 over the taps in row-major order, each term a SELECT on slab(t) == k:
+ *        q0 = sum_t w_k(t) (slab(t)==k ? x0 : 0),      a0 = sum_t w_k(t) (slab(t)==k ? m0 : 0),
+ *        q1 = sum_t w_{k+1}(t) (slab(t)==k ? x1 : 0),  a1 = sum_t w_{k+1}(t) (slab(t)==k ? m1 : 0)     (both exactly 0 for k = L-1),
+ *      then q_k = fl(q0 + q1), a_k = fl(a0 + a1).  A NaN on a hole or on another slab's texel never reaches the output.
+ *   4. Steps 6 and 7 of the contract above with q_k, a_k for q_l, a_l: T = 1, V = 0, A = 0; for k = 0 .. L-1: V = fma(T, q_k, V),
+ *      A = fma(T, a_k, A), T = T * max(1 - a_k, 0); out = V / A where A > 0, else 0 (normalize == 0: out = V); coverage = A.
+ * The image is expected finite on every texel that is not a hole (0 * Inf in x1 is not defined here).  Consequences that hold exactly:
+ * integral coordinates (holes as NaN or < 0) give aadff_render_psf_map_stack_occluded on the same indices bit for bit (m0 = 1, x0 = x,
+ * every term of q1, a1 an exact 0; the kernel skips that pass where no staged texel of the slab has f != 0); L = 1 gives the hard L = 1
+ * render for every pos >= 0; pos > L-1 gives what pos = L-1 gives; a slab with no texel in the window changes nothing; a power-of-two
+ * image scale scales V alike; a repeat equals itself, a stack its slices and a batch its images.  A uniform surface inside one slab
+ * has a_k = 1 up to rounding and hides what lies behind it: only its PSF moves with f.  No atomics, every output written once.
+ * Forward only.  The argument domain and the messages are aadff_render_psf_map_stack_occluded's; NULL pos gives AADFF_EINVAL;
+ * everything is validated before any HIP call. */
+int aadff_render_psf_map_stack_soft_occluded(const float* img, const float* psf_maps, const float* pos, float* out,
+                                             float* coverage_or_null, int B, int C, int S, int L, int H, int W, int grid, int ks,
+                                             int normalize, aadff_stream_t stream);
+
 /* Measurement aid (no reference counterpart): arm the NEXT aadff_render_psf_map_stack (slice-batched kernel: ks 11, S >= 3)
  * or aadff_psf_points / aadff_psf_points_staged call made by this host thread so that its kernel is launched with the two
  * HIP events (hipEvent_t, timing enabled) attached to the dispatch (hipExtLaunchKernelGGL): hipEventElapsedTime then gives
